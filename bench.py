@@ -2,7 +2,7 @@
 """bench.py — Mcorr/s per ICP iteration on MI355X (BASELINE.json metric), config 4 by default:
 10M <-> 10M synthetic clouds, source sharded over the ranks, target octree replicated.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--points 10000000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--points 10000000] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
     python bench.py --gpus N ...   (N > 1 without a launcher: one process drives the N GPUs,
                                     icp_hip_create_multi; the drop-in's single-process path)
@@ -13,27 +13,36 @@ the resident source + exact octree NN + residual + 3-sigma statistics (RCCL all-
 (ICP_FLAG_NO_EARLY_STOP) so exactly K iterations are timed.
 
 Rank 0 prints ONE JSON line. `value` = the points of all ranks x K / the wall time of the K timed
-iterations (max over ranks); `median` = the same rate from the median iteration of 2..K
-(SURVEY.md §8d). Extra objects:
+iterations (max over ranks); `ms_per_step` = that wall time / K; `median` = the same rate from the
+median iteration of 2..K.
+
+A plain run sets up, warms up, times the K iterations and prints the line: nothing else runs.
+--dump-outputs DIR then writes what the last timed iteration left for a caller (see dump_outputs;
+one process only). --warmup 0 runs no untimed step: the first iteration is then the first timed one.
+--full adds the legs that take runs of their own (search_paths, reference_work, cpu_baseline,
+cpu_allcores, timed_state_parity, registration, parity; null in a plain line); the --no-* options
+switch single legs of a --full run off. Extra objects:
   roofline      the search kernel k_nn_wave: its compulsory HBM bytes per launch (DESIGN.md §3.1:
                 64 B per query streamed + every target point (28 B) and node (56 B) once) / its
                 average HIP-event duration over the timed iterations; `traffic` = PMC bytes per
                 launch (rocprofv3, calibrated per access width: tools/calib_pmc.sh) of the same
                 kernel source, or null; `fabric_gbs` = those bytes over this run's kernel time
                 (L2 -> fabric requests, Infinity-Cache hits included: not an HBM rate).
-  reference_work  SURVEY.md §8d's model of the reference DFS's work (148 + 56 V + 24 P bytes per
+  search_paths  (--full) how the queries of the last timed state split over the wave, ball, per-lane
+                and exact searches: one more iterate from the same state, untimed.
+  reference_work  (--full) SURVEY.md §8d's model of the reference DFS's work (148 + 56 V + 24 P bytes per
                 correspondence): what the reference would move, not what this kernel moves.
-  cpu_baseline  the REFERENCE CPU path (oracle/_ref/ref_bench: icp_registration.cpp's ICP()),
+  cpu_baseline  (--full) the REFERENCE CPU path (oracle/_ref/ref_bench: icp_registration.cpp's ICP()),
                 1 thread, on a bounded sample of the same workload (rank 0, N=1 only).
-  cpu_allcores  the CPU restatement (oracle/icp_oracle.c, OpenMP NN loop) on every core of this
+  cpu_allcores  (--full) the CPU restatement (oracle/icp_oracle.c, OpenMP NN loop) on every core of this
                 process's CPU set, full size, from the parity leg below.
-  timed_state_parity  (N=1) the correspondences and residuals of the LAST TIMED iterate (the
+  timed_state_parity  (--full, N=1) the correspondences and residuals of the LAST TIMED iterate (the
                 candidate-cache state the figure was measured in) against the CPU oracle's octree
                 NN on the same moved source, every query: mismatch counts (bit for bit).
-  registration  (N=1) a registration of the full clouds with the reference's stops on
+  registration  (--full, N=1) a registration of the full clouds with the reference's stops on
                 (ICPParameters defaults): iterations taken, wall, mean Mcorr/s over all iterates
                 including the first, the first iterate's share.
-  parity        (N=1) a fresh engine registration of the full clouds for --parity-iters
+  parity        (--full, N=1) a fresh engine registration of the full clouds for --parity-iters
                 iterations on the GPU and on the CPU oracle: final transform RMSE (north star:
                 <= 1e-6), per-iteration valid counts, final RMSE.
 """
@@ -248,6 +257,30 @@ def parity_leg(icp, ctx, tgt: np.ndarray, src: np.ndarray, iters: int) -> tuple[
     return parity, allcores
 
 
+DUMP_SAMPLE = 1_000_000  # rows of the per-query outputs kept by --dump-outputs (48 B per row)
+
+
+def dump_outputs(out_dir: str, ctx, sess) -> None:
+    """What the timed path computed in its last step, as a caller of the session receives it:
+    the accumulated transform, the moved source and its correspondences (target index, residual).
+    One .npy per array, float64. Clouds larger than DUMP_SAMPLE rows are written as a fixed sample
+    of rows (seed 0, ascending; the row numbers go to sample_rows.npy), so the whole is <= 64 MB
+    and two builds run with the same arguments write the same rows. One process only (main refuses
+    it under a launcher, where each rank holds only its shard of the source)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    moved = ctx.get_source()
+    idx, dist = ctx.get_correspondences()
+    m = len(moved)
+    rows = np.arange(m) if m <= DUMP_SAMPLE else np.sort(
+        np.random.default_rng(0).choice(m, size=DUMP_SAMPLE, replace=False))
+    np.save(d / "transform.npy", np.ascontiguousarray(sess.transform(), dtype=np.float64))
+    np.save(d / "sample_rows.npy", rows.astype(np.float64))
+    np.save(d / "source_moved.npy", np.ascontiguousarray(moved[rows], dtype=np.float64))
+    np.save(d / "correspondence_index.npy", idx[rows].astype(np.float64))
+    np.save(d / "correspondence_distance.npy", np.ascontiguousarray(dist[rows], dtype=np.float64))
+
+
 class stdout_to_stderr:
     """RCCL prints a version banner on file descriptor 1 when a communicator is created; the bench
     contract is ONE JSON line on stdout, so native writes go to stderr while RCCL initialises."""
@@ -274,10 +307,17 @@ def main() -> int:
     ap.add_argument("--points", type=int, default=10_000_000, help="points per cloud (config 4: 10M)")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000)
     ap.add_argument("--parity-iters", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: search-path split, reference work "
+                         "model, CPU baselines, parity against the CPU oracle, a stops-on registration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (transform, moved source, "
+                         "correspondences; a fixed sample of rows above 1M points) as DIR/<name>.npy; "
+                         "one process only, not under torchrun")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the CPU checks (the timed state's correspondences and the fresh registration)")
-    ap.add_argument("--no-registration", action="store_true", help="skip the stops-on registration leg")
+                    help="--full: skip the CPU checks (the timed state's correspondences and the fresh registration)")
+    ap.add_argument("--no-registration", action="store_true", help="--full: skip the stops-on registration leg")
     ap.add_argument("--prewarm-ms", type=float, default=0.0,
                     help="diagnostic: keep the GPU busy with a matrix loop this long before the warmup steps")
     ap.add_argument("--exchange", choices=("rccl", "host"), default="rccl",
@@ -305,6 +345,8 @@ def main() -> int:
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and world > 1:
+        ap.error("--dump-outputs needs one process (each rank of a launcher holds only its source shard)")
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     import torch
@@ -387,8 +429,11 @@ def main() -> int:
             torch.cuda.synchronize()
         del a_
     # warmup; the first iteration (no previous residuals: the guess is a descent) is reported alone
-    first_ms = sess.step_n_timed(1)
-    first_nn_ms, _ = ctx.timings(1)
+    # (--warmup 0: no untimed step at all, the first iteration is the first timed one)
+    first_ms = first_nn_ms = None
+    if args.warmup > 0:
+        first_ms = sess.step_n_timed(1)
+        first_nn_ms, _ = ctx.timings(1)
     if args.warmup > 1:
         sess.step_n_timed(args.warmup - 1)
     ctx.synchronize()
@@ -431,18 +476,20 @@ def main() -> int:
                 "note": "count/rank/device: RCCL's own view (icp_hip_comm_info); exchange_ms: the two per-iteration "
                         "record all-gathers (HIP events on the compute stream, includes waiting for the slowest "
                         "peer; host clock for the host exchange), timed iterates (every 8th) of the timed region"}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, sess)
     # untimed: the state the last timed iterate left (its queries = the moved source, and its
     # correspondences/residuals), checked against the CPU oracle below
     timed_q = timed_idx = timed_d = None
-    if rank == 0 and world == 1 and not args.no_parity:
+    if args.full and rank == 0 and world == 1 and not args.no_parity:
         timed_q = ctx.get_source()
         timed_idx, timed_d = ctx.get_correspondences()
     # untimed: how the last timed state splits over the search paths (same queries, same guess)
-    probe = ctx.iterate(None, 1, icp.RULES_ENGINE, 3.0)
+    probe = ctx.iterate(None, 1, icp.RULES_ENGINE, 3.0) if args.full else None
     rc, res = sess.finish()
     sess.close()
     # v, p of the reference DFS on this rank's queries (untimed; COUNT build of the parity kernel)
-    v_mean, p_mean = ctx.traversal_counts() if rank == 0 else (None, None)
+    v_mean, p_mean = ctx.traversal_counts() if args.full and rank == 0 else (None, None)
 
     info = ctx.target_info()
     n_local = n // shards if group else hi - lo  # per device
@@ -478,7 +525,7 @@ def main() -> int:
     value = n * args.steps / elapsed / 1e6
 
     cpu = allcores = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(tgt, src, args.cpu_sample)
         except Exception as e:  # keep the bench line even if the baseline cannot run
@@ -491,12 +538,12 @@ def main() -> int:
             timed_parity = {"error": str(e)}
         del timed_q, timed_idx, timed_d
     registration = None
-    if rank == 0 and world == 1 and not args.no_registration:
+    if args.full and rank == 0 and world == 1 and not args.no_registration:
         try:
             registration = registration_leg(icp, ctx, src)
         except Exception as e:
             registration = {"error": str(e)}
-    if rank == 0 and world == 1 and not args.no_parity and args.parity_iters > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_parity and args.parity_iters > 0:
         try:
             parity, allcores = parity_leg(icp, ctx, tgt, src, args.parity_iters)
         except Exception as e:
@@ -538,7 +585,7 @@ def main() -> int:
             },
             "median": {"iter_ms": round(med_ms, 4), "value": round(n / med_ms / 1e3, 3),
                        "over": f"iterations 2..{args.steps} of the timed region (host wall per step, max over ranks)"},
-            "first_iteration": {"ms": round(float(first_ms[0]), 4), "search_kernel_ms": round(float(first_nn_ms[0]), 4),
+            "first_iteration": None if first_ms is None else {"ms": round(float(first_ms[0]), 4), "search_kernel_ms": round(float(first_nn_ms[0]), 4),
                                 "note": "no previous matches: the guesses are a descent, its sibling leaves and the other lanes' "
                                         "points (k_nn_wave<false>), every wave walks, full cull pass; kernels loaded by the "
                                         "context's process warm-up (icp_hip_config.no_warmup)"},
@@ -558,7 +605,7 @@ def main() -> int:
                 "iterate_device_ms_avg": round(float(np.mean(it_ms)), 4),
                 "model": f"{STREAM_B_PER_QUERY} B/query streamed + {TGT_B_PER_POINT} B/target point + {NODE_B} B/node, each once",
             },
-            "search_paths": {"queries": n_local * (shards if group else 1),
+            "search_paths": None if probe is None else {"queries": n_local * (shards if group else 1),
                              "wave": n_local * (shards if group else 1) - int(probe.n_ball_search),
                              "ball": int(probe.n_ball_search), "lane": int(probe.n_lane_search),
                              "exact_fallback": int(probe.n_fallback),

@@ -5,7 +5,7 @@ parent never touches the GPU).
 usage: python3 tools/ab_bench.py REPS LIB_A LIB_B -- BENCH_ARGS...
   LIB_* = a path to a libicp_hip*.so, or "cur" (the in-tree libicp_hip.so)
 One summary line per run: value, median, search kernel ms (HIP events), iterate device ms,
-registration wall ms (when the leg ran).
+registration wall ms and timed-state mismatches (when the legs ran: BENCH_ARGS with --full).
 """
 import json
 import os

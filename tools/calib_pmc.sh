@@ -1,11 +1,11 @@
 #!/bin/bash
 # FETCH_SIZE / WRITE_SIZE calibration for the search kernel's access widths (tools/fetch_calib.hip).
 # Build here first:  hipcc --offload-arch=gfx950 -O3 -o tools/fetch_calib tools/fetch_calib.hip
-# usage (gpurun, repo root): bash tools/calib_pmc.sh TAG
+# usage (repo root; results go to $ICP_OUT, default measurements/): bash tools/calib_pmc.sh TAG
 set -u
 TAG=${1:-calib}
 REPO=$(pwd)
-OUT=$REPO/gpurun_out/calib_$TAG
+OUT=$REPO/${ICP_OUT:-measurements}/calib_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 BIN=$REPO/tools/fetch_calib

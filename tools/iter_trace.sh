@@ -1,14 +1,14 @@
 #!/bin/bash
 # Per-iterate trace of the bench workload (tools/iter_trace.py) plus per-dispatch PMC passes of
-# the same iterates. Run through gpurun from the repo root:
+# the same iterates. Run from the repo root:
 #   bash tools/iter_trace.sh TAG [ITERS] [N]
-# Output: gpurun_out/itr_TAG/{times,corr,dbg}.jsonl and pmc_*/ (rocprofv3 counter_collection.csv)
+# Output: $ICP_OUT/itr_TAG/ (default measurements/): {times,corr,dbg}.jsonl and pmc_*/ (rocprofv3 counter_collection.csv)
 set -u
 TAG=${1:-itr}
 ITERS=${2:-50}
 N=${3:-10000000}
 REPO=$(pwd)
-OUT=$REPO/gpurun_out/itr_$TAG
+OUT=$REPO/${ICP_OUT:-measurements}/itr_$TAG
 mkdir -p "$OUT"
 timeout -k 10 300 python3 -u tools/iter_trace.py $N $ITERS --no-corr > "$OUT/times.jsonl" 2> "$OUT/times.err" || { tail -20 "$OUT/times.err"; exit 1; }
 timeout -k 10 300 python3 -u tools/iter_trace.py $N $ITERS --dbg > "$OUT/corr_dbg.jsonl" 2> "$OUT/corr_dbg.err" || { tail -20 "$OUT/corr_dbg.err"; exit 1; }

@@ -8,7 +8,7 @@ N=${2:-10000000}
 STEPS=${STEPS:-20}
 WARMUP=${WARMUP:-5}
 REPO=$(pwd)
-OUT=$REPO/gpurun_out/prof_$TAG
+OUT=$REPO/${ICP_OUT:-measurements}/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 # BENCH_EXTRA: workload arguments of bench.py (e.g. --scene); WORKLOAD: its bench.py workload_key

@@ -1,12 +1,12 @@
 #!/bin/bash
 # SQ counter passes on the search kernel k_nn_wave<true> (steady-state launches), 10M, 3 timed
-# steps + 2 warmup. One rocprofv3 run per counter set (gpurun's rule: <= 8 SQ counters a pass).
-# usage (gpurun, repo root): bash tools/sq_wave.sh TAG [bench.py args, e.g. --config KEY=VALUE]
+# steps + 2 warmup. One rocprofv3 run per counter set (at most 8 SQ counters a pass).
+# usage (repo root; results go to $ICP_OUT, default measurements/): bash tools/sq_wave.sh TAG [bench.py args, e.g. --config KEY=VALUE]
 set -u
 TAG=${1:-sq}
 shift || true
 EXTRA="$*"
-REPO=$(pwd); OUT=$REPO/gpurun_out/sq_$TAG; rm -rf $OUT; mkdir -p $OUT; export TMPDIR=/tmp
+REPO=$(pwd); OUT=$REPO/${ICP_OUT:-measurements}/sq_$TAG; rm -rf $OUT; mkdir -p $OUT; export TMPDIR=/tmp
 cd /tmp
 i=0
 for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" \

@@ -4,7 +4,7 @@ import csv
 import glob
 import sys
 
-d = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/tl"
+d = sys.argv[1] if len(sys.argv) > 1 else "measurements/tl"
 rows = []
 for f in glob.glob(f"{d}/**/*kernel_trace.csv", recursive=True):
     rows += list(csv.DictReader(open(f)))

@@ -4,7 +4,7 @@
 set -u
 TAG=$1; shift
 R=$(pwd)
-OUT=$R/gpurun_out/trace_$TAG
+OUT=$R/${ICP_OUT:-measurements}/trace_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
