@@ -153,9 +153,9 @@ typedef struct icp_hip_config {
                               launch, which otherwise lands in the first real iterate (+1.3 ms
                               at 10M); 1: no warm-up                                     dflt 0 */
   int32_t ball_mode;       /* k_nn_ball, the queries the wave search left: 0 a whole query per wave
-                              (the cooperative search from the cell tables of its bound) when the
-                              list is short (<= one per wave of the launch) or long (> four per
-                              wave: an unconverged registration on surface data), else four
+                              (the cooperative search from the cell tables of its bound) only
+                              when the list is long (> four per wave of the launch: an unconverged
+                              registration on surface data) or after the wide pass, else four
                               queries per wave (16-lane ball walks, follow-ups for the balls that
                               overflow); 1 always the ball walk; 2 always whole queries. The same
                               results either way                          dflt 0 */

@@ -1,5 +1,5 @@
-// kernels.h — launch wrappers of the gfx950 kernels (nn_kernels.hip, reduce_kernels.hip,
-// util_kernels.hip). Internal C++ API used by the C-ABI context (icp_ctx.hip); no torch types.
+// kernels.h — launch wrappers of the gfx950 kernels (nn_kernels.hip, nn_ball.hip,
+// reduce_kernels.hip, util_kernels.hip). Internal C++ API used by the C-ABI context (icp_ctx.hip); no torch types.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -127,7 +127,13 @@ struct NNLaunch {
 
 // Threads per block of the per-thread search kernels for a given stack depth.
 int nn_block_threads(int levels);
+// The correspondence search of one iterate (nn_kernels.hip): the reference-order kernel, or the
+// wave search, its second passes and the follow-up search.
 hipError_t launch_nn(const NNLaunch& a, hipStream_t s);
+// launch_nn's parts in nn_ball.hip: the reference-order kernel (k_nn_ref), and the follow-up search
+// of the lists the wave search left (k_nn_ball; owns its LDS sizing and the ball_mode rule).
+hipError_t launch_nn_ref(const NNLaunch& a, hipStream_t s);
+hipError_t launch_nn_follow(const NNLaunch& a, hipStream_t s);
 // TgtPt::sep of every target point (lower bound of its distance to every other point).
 hipError_t launch_target_sep(const NodeRec* nodes, TgtPt* pts, int64_t n, int levels, hipStream_t s);
 hipError_t launch_mark_copies(TgtPt* pts, int64_t n, hipStream_t s);

@@ -323,6 +323,67 @@ __device__ __forceinline__ double residual_to(const TgtPt* pts, int32_t pos, dou
   return __builtin_sqrt(dx * dx + dy * dy + dz * dz);
 }
 
+// ---- shared pieces of the searches
+
+// fl(d2) from q to a target point exactly as the reference's leaf scan computes it
+// (octree.cpp:139-144), in the two load shapes the kernels use: (x, y) as one 16-B load and z, or
+// three scalar loads.
+__device__ __forceinline__ double d2_to(const TgtPt* p, double qx, double qy, double qz) {
+  const double2 pxy = *reinterpret_cast<const double2*>(&p->x);
+  const double dx = pxy.x - qx, dy = pxy.y - qy, dz = p->z - qz;
+  return dx * dx + dy * dy + dz * dz;
+}
+__device__ __forceinline__ double d2_to_s(const TgtPt* p, double qx, double qy, double qz) {
+  const double dx = p->x - qx, dy = p->y - qy, dz = p->z - qz;
+  return dx * dx + dy * dy + dz * dz;
+}
+
+// A node record's box: three 16-B loads of its 64-B line (lo x, y | lo z, hi x | hi y, z).
+struct NodeBox {
+  double2 l01, l2h0, h12;
+};
+__device__ __forceinline__ NodeBox load_node_box(const NodeRec* rr) {
+  NodeBox n;
+  n.l01 = *reinterpret_cast<const double2*>(&rr->lo[0]);
+  n.l2h0 = *reinterpret_cast<const double2*>(&rr->lo[2]);
+  n.h12 = *reinterpret_cast<const double2*>(&rr->hi[1]);
+  return n;
+}
+// A node record loaded whole: four 16-B loads of one 64-B line, all in flight together.
+struct NodeLoad : NodeBox {
+  int4 topo;  // first, meta, depth, pad
+};
+__device__ __forceinline__ NodeLoad load_node(const NodeRec* rr) {
+  NodeLoad n;
+  n.l01 = *reinterpret_cast<const double2*>(&rr->lo[0]);
+  n.l2h0 = *reinterpret_cast<const double2*>(&rr->lo[2]);
+  n.h12 = *reinterpret_cast<const double2*>(&rr->hi[1]);
+  n.topo = *reinterpret_cast<const int4*>(&rr->first);
+  return n;
+}
+
+// The children of the box [l, h] seen from q: the box's midpoint and, per axis, the squared
+// distance to its lower and upper half. Child o (octant bits x, y, z) has the squared box distance
+// of(o), the same operations as box_s on the child's stored box (its bounds are exactly these
+// values, octree.cpp:97-120).
+struct OctantDist {
+  double mx, my, mz;
+  double sx[2], sy[2], sz[2];
+  __device__ __forceinline__ double of(int o) const { return sx[o & 1] + sy[(o >> 1) & 1] + sz[o >> 2]; }
+};
+__device__ __forceinline__ OctantDist octant_dist(double lx, double ly, double lz, double hx, double hy, double hz,
+                                                  double qx, double qy, double qz) {
+  OctantDist d;
+  d.mx = (lx + hx) / 2, d.my = (ly + hy) / 2, d.mz = (lz + hz) / 2;
+  const double ax0 = smax(0.0, smax(lx - qx, qx - d.mx)), ax1 = smax(0.0, smax(d.mx - qx, qx - hx));
+  const double ay0 = smax(0.0, smax(ly - qy, qy - d.my)), ay1 = smax(0.0, smax(d.my - qy, qy - hy));
+  const double az0 = smax(0.0, smax(lz - qz, qz - d.mz)), az1 = smax(0.0, smax(d.mz - qz, qz - hz));
+  d.sx[0] = ax0 * ax0, d.sx[1] = ax1 * ax1;
+  d.sy[0] = ay0 * ay0, d.sy[1] = ay1 * ay1;
+  d.sz[0] = az0 * az0, d.sz[1] = az1 * az1;
+  return d;
+}
+
 // ---- the reference DFS, verbatim order
 
 // Stack entry: bits 0..31 first child record, bits 32..55 up to 8 pending children as 3-bit
@@ -343,12 +404,9 @@ __device__ __forceinline__ void exact_dfs(const NNLaunch& a, double qx, double q
   bool siblings_on_top = false;
   if (COUNT) visits += 1.0;
   while (true) {
-    const NodeRec* r = a.nodes + node;
-    const double2 l01 = *reinterpret_cast<const double2*>(&r->lo[0]);
-    const double2 l2h0 = *reinterpret_cast<const double2*>(&r->lo[2]);
-    const double2 h12 = *reinterpret_cast<const double2*>(&r->hi[1]);
-    const int4 topo = *reinterpret_cast<const int4*>(&r->first);
-    const double lx = l01.x, ly = l01.y, lz = l2h0.x, hx = l2h0.y, hy = h12.x, hz = h12.y;
+    const NodeLoad nd = load_node(a.nodes + node);
+    const int4 topo = nd.topo;
+    const double lx = nd.l01.x, ly = nd.l01.y, lz = nd.l2h0.x, hx = nd.l2h0.y, hy = nd.h12.x, hz = nd.h12.y;
     const double m = box_dist(lx, ly, lz, hx, hy, hz, qx, qy, qz);
     const int32_t first = topo.x;
     const uint32_t meta = (uint32_t)topo.y;
@@ -361,12 +419,7 @@ __device__ __forceinline__ void exact_dfs(const NNLaunch& a, double qx, double q
       if (COUNT) scanned += (double)cnt;
       for (int32_t k = 0; k < cnt; k++) {
         const TgtPt* p = a.pts + first + k;
-        const double2 pxy = *reinterpret_cast<const double2*>(&p->x);
-        const double pz = p->z;
-        const double dx = pxy.x - qx;
-        const double dy = pxy.y - qy;
-        const double dz = pz - qz;
-        const double d2 = dx * dx + dy * dy + dz * dz;
+        const double d2 = d2_to(p, qx, qy, qz);
         if (d2 < best_d2) {  // strict <, ascending original index inside a leaf
           best_d2 = d2;
           best = first + k;
@@ -375,17 +428,11 @@ __device__ __forceinline__ void exact_dfs(const NNLaunch& a, double qx, double q
     } else {
       // Inner node: distances of the existing children from the parent box and its
       // midpoint (the stored child boxes are exactly these values, octree.cpp:97-120).
-      const double mx = (lx + hx) / 2, my = (ly + hy) / 2, mz = (lz + hz) / 2;
-      const double ax0 = smax(0.0, smax(lx - qx, qx - mx)), ax1 = smax(0.0, smax(mx - qx, qx - hx));
-      const double ay0 = smax(0.0, smax(ly - qy, qy - my)), ay1 = smax(0.0, smax(my - qy, qy - hy));
-      const double az0 = smax(0.0, smax(lz - qz, qz - mz)), az1 = smax(0.0, smax(mz - qz, qz - hz));
-      const double sx[2] = {ax0 * ax0, ax1 * ax1};
-      const double sy[2] = {ay0 * ay0, ay1 * ay1};
-      const double sz[2] = {az0 * az0, az1 * az1};
+      const OctantDist od = octant_dist(lx, ly, lz, hx, hy, hz, qx, qy, qz);
       const uint32_t mask = meta & 0xffu;
       double cd[8];
 #pragma unroll
-      for (int o = 0; o < 8; o++) cd[o] = __builtin_sqrt(sx[o & 1] + sy[(o >> 1) & 1] + sz[o >> 2]);
+      for (int o = 0; o < 8; o++) cd[o] = __builtin_sqrt(od.of(o));
       // Stable order = sort by (distance, octant): rank = #children strictly before.
       uint32_t rk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -492,12 +539,7 @@ __device__ __forceinline__ bool fast_dfs(const NNLaunch& a, double qx, double qy
         const int32_t cnt = (int32_t)(meta & ~kLeafBit);
         for (int32_t k = 0; k < cnt; k++) {
           const TgtPt* p = a.pts + first + k;
-          const double2 pxy = *reinterpret_cast<const double2*>(&p->x);
-          const double pz = p->z;
-          const double dx = pxy.x - qx;
-          const double dy = pxy.y - qy;
-          const double dz = pz - qz;
-          const double d2 = dx * dx + dy * dy + dz * dz;
+          const double d2 = d2_to(p, qx, qy, qz);
           if (d2 < best) {
             second = best;
             best = d2;
@@ -564,11 +606,8 @@ __device__ __forceinline__ bool fast_dfs(const NNLaunch& a, double qx, double qy
       if (rem == 0) sp--;
       else st[(sp - 1) * bs] = (e & ~(0xffull << 32)) | ((unsigned long long)rem << 32);
       node = first + __builtin_popcount(pmask & ((1u << o) - 1u));
-      const NodeRec* r = a.nodes + node;
-      const double2 l01 = *reinterpret_cast<const double2*>(&r->lo[0]);
-      const double2 l2h0 = *reinterpret_cast<const double2*>(&r->lo[2]);
-      const double2 h12 = *reinterpret_cast<const double2*>(&r->hi[1]);
-      lx = l01.x; ly = l01.y; lz = l2h0.x; hx = l2h0.y; hy = h12.x; hz = h12.y;
+      const NodeBox nb = load_node_box(a.nodes + node);
+      lx = nb.l01.x; ly = nb.l01.y; lz = nb.l2h0.x; hx = nb.l2h0.y; hy = nb.h12.x; hz = nb.h12.y;
       s = box_s(lx, ly, lz, hx, hy, hz, qx, qy, qz);
       found = true;
       break;
@@ -712,23 +751,9 @@ __device__ __forceinline__ int cell_starts(const NNLaunch& a, double blx, double
   return count;
 }
 
-// A node record loaded whole: four 16-B loads of one 64-B line, all in flight together.
-struct NodeLoad {
-  double2 l01, l2h0, h12;
-  int4 topo;  // first, meta, depth, pad
-};
-__device__ __forceinline__ NodeLoad load_node(const NodeRec* rr) {
-  NodeLoad n;
-  n.l01 = *reinterpret_cast<const double2*>(&rr->lo[0]);
-  n.l2h0 = *reinterpret_cast<const double2*>(&rr->lo[2]);
-  n.h12 = *reinterpret_cast<const double2*>(&rr->hi[1]);
-  n.topo = *reinterpret_cast<const int4*>(&rr->first);
-  return n;
-}
-
 // Children of an inner node that meet the closed box [bl, bh] (child o spans [lo or mid,
 // mid or hi] per axis, octree.cpp:115-120), as a bit mask over octants.
-__device__ __forceinline__ uint32_t children_in_box(const NodeLoad& n, uint32_t mask, double blx, double bly,
+__device__ __forceinline__ uint32_t children_in_box(const NodeBox& n, uint32_t mask, double blx, double bly,
                                                     double blz, double bhx, double bhy, double bhz) {
   const double lx = n.l01.x, ly = n.l01.y, lz = n.l2h0.x, hx = n.l2h0.y, hy = n.h12.x, hz = n.h12.y;
   const double mx = (lx + hx) / 2, my = (ly + hy) / 2, mz = (lz + hz) / 2;
@@ -747,10 +772,8 @@ __device__ __forceinline__ uint32_t children_in_box(const NodeLoad& n, uint32_t 
 // Children of an inner node whose squared box distance to q is <= thr (sphere test).
 __device__ __forceinline__ uint32_t children_in_ball(const NodeRec* rr, uint32_t mask, double qx, double qy,
                                                      double qz, double thr) {
-  const double2 l01 = *reinterpret_cast<const double2*>(&rr->lo[0]);
-  const double2 l2h0 = *reinterpret_cast<const double2*>(&rr->lo[2]);
-  const double2 h12 = *reinterpret_cast<const double2*>(&rr->hi[1]);
-  const double lx = l01.x, ly = l01.y, lz = l2h0.x, hx = l2h0.y, hy = h12.x, hz = h12.y;
+  const NodeBox n = load_node_box(rr);
+  const double lx = n.l01.x, ly = n.l01.y, lz = n.l2h0.x, hx = n.l2h0.y, hy = n.h12.x, hz = n.h12.y;
   const double mx = (lx + hx) / 2, my = (ly + hy) / 2, mz = (lz + hz) / 2;
   const double ax0 = smax(0.0, smax(lx - qx, qx - mx)), ax1 = smax(0.0, smax(mx - qx, qx - hx));
   const double ay0 = smax(0.0, smax(ly - qy, qy - my)), ay1 = smax(0.0, smax(my - qy, qy - hy));

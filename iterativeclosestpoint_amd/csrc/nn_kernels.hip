@@ -4,14 +4,13 @@
 // (core/icpengine.cpp:169-184 -> octree.cpp:128-184; CLI icp_registration.cpp:481-496).
 // Every kernel returns, for each query, exactly the index and residual the reference DFS returns.
 //
-//  k_nn_ref    one thread per query, the literal reference-order DFS (the parity kernel, and the
-//              work counter of the roofline's "reference work" figure).
 //  k_nn_wave   the product search: 64 spatially coherent queries per wave share one search box,
 //              one cooperative walk of the octree, one lockstep fp32 filter scan, and a rigorous
 //              per-query certificate (nn_device.h) that the reference returns the same point.
-//  k_nn_ball   the queries a wave did not take, four per wave (16-lane groups), sphere walks; what
-//              those cannot decide, and the wave search's exact list: per-lane certified search,
-//              else the reference-order DFS.
+//  k_nn_half   the second pass over the 32-query halves of the waves whose box overflowed.
+//  k_nn_wide   the wide pass: an overflowed box walked and scanned in segments.
+// The queries these leave go to the follow-up search (k_nn_ball, nn_ball.hip); the reference-order
+// kernel (k_nn_ref) lives there too.
 //
 // Everything is fp64 except the scan's filter, whose result is re-evaluated in fp64; built with
 // -ffp-contract=off (the reference is built without FMA).
@@ -59,47 +58,6 @@ namespace {
 
 using namespace dev;
 
-// ---------------------------------------------------------------------------------------------
-// The reference-order kernel.
-template <bool APPLY, bool COUNT>
-__global__ void __launch_bounds__(256) k_nn_ref(NNLaunch a) {
-  if (a.loop && a.loop->core.done) return;  // the device loop's session finished
-  extern __shared__ __attribute__((aligned(16))) unsigned long long lds_stack[];
-  const int bs = blockDim.x;
-  const int64_t i = (int64_t)blockIdx.x * bs + threadIdx.x;
-  const bool active = i < a.n;
-
-  double qx = 0.0, qy = 0.0, qz = 0.0;
-  load_query<APPLY>(a, i, active, qx, qy, qz);
-
-  double best_d2 = a.init_best;
-  int32_t best = -1;
-  double visits = 0.0, scanned = 0.0;
-  // A NaN coordinate makes every leaf distance NaN, so the reference never updates best_idx
-  // (octree.cpp:146): skipping the search is exact. (Its box distances stay finite: max(0,NaN)=0.)
-  const bool nan_q = (qx != qx) || (qy != qy) || (qz != qz);
-  if (active && !nan_q && a.n_nodes > 0)
-    exact_dfs<COUNT>(a, qx, qy, qz, lds_stack + threadIdx.x, bs, best, best_d2, visits, scanned);
-  if (active) {
-    const int32_t pos = best >= 0 ? best : a.pos0;
-    a.pos_out[i] = pos;
-    a.dist_out[i] = best >= 0 ? __builtin_sqrt(best_d2)  // == computeDistance bit for bit
-                              : residual_to(a.pts, a.pos0, qx, qy, qz);
-  }
-  if (COUNT) {
-    __syncthreads();  // every traversal is done: reuse the stack LDS for the reduction
-    double c[2] = {visits, scanned};
-    block_sum<2>(c, reinterpret_cast<double*>(lds_stack));
-    if (threadIdx.x == 0) {
-      atomicAdd(&a.counters[0], (unsigned long long)c[0]);
-      atomicAdd(&a.counters[1], (unsigned long long)c[1]);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The wave search.
-//
 // The 64 queries of a wave are one kd bucket of the source: spatially compact.
 //  1. Guess u >= each query's nearest squared distance: after an iteration on the same queries,
 //     (previous residual + displacement)^2 (triangle inequality); otherwise one nearest-child
@@ -233,7 +191,7 @@ __device__ __forceinline__ void wave_record(const NNLaunch& a, uint32_t wid, int
   if (wballot(active && !settled) != 0) {
     if (lane == 0) {
       rec->flag = 1ull;
-      if (DBG && kDbgCounts && a.dbg) atomicAdd(&a.dbg[30], 1ull);
+      if (DBG && kDbgCounts && a.dbg) atomicAdd(&a.dbg[ICP_DBG_FZ_RECOMPUTE], 1ull);
     }
     return;
   }
@@ -259,7 +217,7 @@ __device__ __forceinline__ void wave_record(const NNLaunch& a, uint32_t wid, int
     rec->cnt = (double)__popcll(am);
     rec->bm = bm;
     rec->flag = 0ull;
-    if (DBG && kDbgCounts && a.dbg) atomicAdd(&a.dbg[31], (unsigned long long)__popcll(bm));
+    if (DBG && kDbgCounts && a.dbg) atomicAdd(&a.dbg[ICP_DBG_FZ_BAND], (unsigned long long)__popcll(bm));
   }
 }
 static_assert(kStatLds <= kWaveLds, "the record's reduction fits the wave's LDS area");
@@ -324,9 +282,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
     // the previous match is a candidate: its fl(d2) from the moved query bounds the nearest
     // point's (usually well below (previous residual + displacement)^2)
     const TgtPt* pp = a.pts + prev_pos;
-    const double2 pxy = *reinterpret_cast<const double2*>(&pp->x);
-    const double dx = pxy.x - qx, dy = pxy.y - qy, dz = pp->z - qz;
-    u = dx * dx + dy * dy + dz * dz;
+    u = d2_to(pp, qx, qy, qz);
     if (CERT) safe = prev_certified(u, pp->sep, a.init_best);
   } else if (active && finite_q) {
     int32_t node = 0;
@@ -355,9 +311,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
     auto scan_leaf = [&](int2 topo) {
       const int32_t cnt = (int32_t)((uint32_t)topo.y & ~kLeafBit);
       for (int32_t k = 0; k < cnt; k++) {
-        const TgtPt* p = a.pts + topo.x + k;
-        const double dx = p->x - qx, dy = p->y - qy, dz = p->z - qz;
-        const double d2 = dx * dx + dy * dy + dz * dz;
+        const double d2 = d2_to_s(a.pts + topo.x + k, qx, qy, qz);
         const bool t = d2 < u;
         u = t ? d2 : u;
         if (!APPLY) gpos = t ? topo.x + k : gpos;
@@ -450,9 +404,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
     }
     const int32_t op = __shfl(gpos, lane ^ bm, kWave);
     if (active && finite_q && bm != 0 && op >= 0) {
-      const TgtPt* p = a.pts + op;
-      const double dx = p->x - qx, dy = p->y - qy, dz = p->z - qz;
-      const double d2 = dx * dx + dy * dy + dz * dz;
+      const double d2 = d2_to_s(a.pts + op, qx, qy, qz);
       u = d2 < u ? d2 : u;
     }
   }
@@ -468,8 +420,8 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
     if (kDbg && a.dbg) {
       const unsigned long long settled = wballot(safe);  // every lane takes part in the ballot
       if (lane == 0) {
-        atomicAdd(&a.dbg[19], (unsigned long long)__popcll(settled));
-        if (open == 0) atomicAdd(&a.dbg[18], 1ull);
+        atomicAdd(&a.dbg[ICP_DBG_PREV_LANES], (unsigned long long)__popcll(settled));
+        if (open == 0) atomicAdd(&a.dbg[ICP_DBG_PREV_WAVES], 1ull);
       }
     }
     if (open == 0 || (a.certify_prev == 3 && __popcll(open) <= kOpenToBall)) {
@@ -622,76 +574,73 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
   auto walk = [&](double wlx, double wly, double wlz, double whx, double why, double whz) {
     nleaf = 0;
     overflow = false;
-      int tail = 1;
-      if (a.cells) {
-        tail = cell_starts<64, kWaveStartK>(a, wlx, wly, wlz, whx, why, whz, lane, 0, queue);
-        if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[21], (unsigned long long)tail);
-      } else {
-        // Wave-uniform descent to the deepest node that holds every leaf meeting B: follow the
-        // only child meeting B while there is exactly one.
-        int32_t start = 0;
-        while (true) {
-          const NodeLoad nd = load_node(a.nodes + start);
-          const int2 topo = make_int2(nd.topo.x, nd.topo.y);
-          const uint32_t meta = (uint32_t)topo.y;
-          if (meta & kLeafBit) break;
-          uint32_t kids = children_in_box(nd, meta & 0xffu, wlx, wly, wlz, whx, why, whz);
-          kids = (uint32_t)__builtin_amdgcn_readfirstlane((int)kids);
-          if (__builtin_popcount(kids) != 1) break;
-          const uint32_t o = (uint32_t)__builtin_ctz(kids);
-          start = __builtin_amdgcn_readfirstlane(topo.x + __builtin_popcount((meta & 0xffu) & ((1u << o) - 1u)));
-          if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[21], 1ull);
-        }
-        if (lane == 0) queue[0] = start;
+    int tail = 1;
+    if (a.cells) {
+      tail = cell_starts<64, kWaveStartK>(a, wlx, wly, wlz, whx, why, whz, lane, 0, queue);
+      if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_START_NODES], (unsigned long long)tail);
+    } else {
+      // Wave-uniform descent to the deepest node that holds every leaf meeting B: follow the
+      // only child meeting B while there is exactly one.
+      int32_t start = 0;
+      while (true) {
+        const NodeLoad nd = load_node(a.nodes + start);
+        const int2 topo = make_int2(nd.topo.x, nd.topo.y);
+        const uint32_t meta = (uint32_t)topo.y;
+        if (meta & kLeafBit) break;
+        uint32_t kids = children_in_box(nd, meta & 0xffu, wlx, wly, wlz, whx, why, whz);
+        kids = (uint32_t)__builtin_amdgcn_readfirstlane((int)kids);
+        if (__builtin_popcount(kids) != 1) break;
+        const uint32_t o = (uint32_t)__builtin_ctz(kids);
+        start = __builtin_amdgcn_readfirstlane(topo.x + __builtin_popcount((meta & 0xffu) & ((1u << o) - 1u)));
+        if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_START_NODES], 1ull);
       }
-      // Every batch pops up to 64 nodes (one per lane), which already meet B (tested by their
-      // parent; the start nodes by the cell box or the descent), appends the points of its leaves
-      // to the candidate list and pushes its children meeting B. Most recent first: the live set
-      // stays small. (Two nodes per lane, both loads in flight, cost the kernel 16 more live
-      // vector registers through this rare path, ~3 % of the waves per iterate: spills on the
-      // common path.)
+      if (lane == 0) queue[0] = start;
+    }
+    // Every batch pops up to 64 nodes (one per lane), which already meet B (tested by their
+    // parent; the start nodes by the cell box or the descent), appends the points of its leaves
+    // to the candidate list and pushes its children meeting B. Most recent first: the live set
+    // stays small. (Two nodes per lane, both loads in flight, cost the kernel 16 more live
+    // vector registers through this rare path, ~3 % of the waves per iterate: spills on the
+    // common path.)
+    wave_lds_fence();
+    while (tail > 0) {
+      const int batch = tail < 64 ? tail : 64;
+      const bool has = lane < batch;
+      // the record's box and topology in one round trip; lanes without a node read the root
+      // (in bounds, ignored)
+      const NodeRec* nr = a.nodes + (has ? queue[tail - batch + lane] : 0);
+      const NodeBox nd = load_node_box(nr);
+      const int2 topo = *reinterpret_cast<const int2*>(&nr->first);
+      const int32_t first = has ? topo.x : 0;
+      const uint32_t meta = has ? (uint32_t)topo.y : 0u;
+      const uint32_t kids = (has && !(meta & kLeafBit)) ? children_in_box(nd, meta & 0xffu, wlx, wly, wlz, whx, why, whz) : 0u;
+      // a leaf contributes its points (contiguous in leaf order) to the candidate list
+      const int lcnt = (has && (meta & kLeafBit)) ? (int)(meta & ~kLeafBit) : 0;
+      int ltot;
+      const int lincl = wave_incl_scan(lcnt, &ltot);
+      const int lpos = nleaf + lincl - lcnt;
+      if (lcnt > 0 && lpos + lcnt <= kWaveCandCap)
+        for (int c = 0; c < lcnt; c++) plist[lpos + c] = first + c;
+      nleaf += ltot;
+      const int nch = __builtin_popcount(kids);
+      int tot;
+      const int incl = wave_incl_scan(nch, &tot);
+      tail -= batch;  // the popped entries are in registers; children overwrite them
+      if (nleaf > kWaveCandCap || tail + tot > kWaveQueue) {
+        overflow = true;
+        return;
+      }
+      int off = tail + incl - nch;
+      uint32_t kk = kids;
+      while (kk) {
+        const uint32_t o = (uint32_t)__builtin_ctz(kk);
+        kk &= kk - 1u;
+        queue[off++] = first + __builtin_popcount(meta & 0xffu & ((1u << o) - 1u));
+      }
+      tail += tot;
+      if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_WALK_BATCHES], 1ull);
       wave_lds_fence();
-      while (tail > 0) {
-        const int batch = tail < 64 ? tail : 64;
-        const bool has = lane < batch;
-        // the record's box and topology in one round trip; lanes without a node read the root
-        // (in bounds, ignored)
-        const NodeRec* nr = a.nodes + (has ? queue[tail - batch + lane] : 0);
-        NodeLoad nd;
-        nd.l01 = *reinterpret_cast<const double2*>(&nr->lo[0]);
-        nd.l2h0 = *reinterpret_cast<const double2*>(&nr->lo[2]);
-        nd.h12 = *reinterpret_cast<const double2*>(&nr->hi[1]);
-        const int2 topo = *reinterpret_cast<const int2*>(&nr->first);
-        const int32_t first = has ? topo.x : 0;
-        const uint32_t meta = has ? (uint32_t)topo.y : 0u;
-        const uint32_t kids = (has && !(meta & kLeafBit)) ? children_in_box(nd, meta & 0xffu, wlx, wly, wlz, whx, why, whz) : 0u;
-        // a leaf contributes its points (contiguous in leaf order) to the candidate list
-        const int lcnt = (has && (meta & kLeafBit)) ? (int)(meta & ~kLeafBit) : 0;
-        int ltot;
-        const int lincl = wave_incl_scan(lcnt, &ltot);
-        const int lpos = nleaf + lincl - lcnt;
-        if (lcnt > 0 && lpos + lcnt <= kWaveCandCap)
-          for (int c = 0; c < lcnt; c++) plist[lpos + c] = first + c;
-        nleaf += ltot;
-        const int nch = __builtin_popcount(kids);
-        int tot;
-        const int incl = wave_incl_scan(nch, &tot);
-        tail -= batch;  // the popped entries are in registers; children overwrite them
-        if (nleaf > kWaveCandCap || tail + tot > kWaveQueue) {
-          overflow = true;
-          return;
-        }
-        int off = tail + incl - nch;
-        uint32_t kk = kids;
-        while (kk) {
-          const uint32_t o = (uint32_t)__builtin_ctz(kk);
-          kk &= kk - 1u;
-          queue[off++] = first + __builtin_popcount(meta & 0xffu & ((1u << o) - 1u));
-        }
-        tail += tot;
-        if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[5], 1ull);
-        wave_lds_fence();
-      }
+    }
   };
   // The wide pass (WIDE): the same walk over a box of any size, in segments. A batch whose leaves
   // would overflow the candidate list appends the ones that fit (a prefix of its leaf lanes: the
@@ -729,10 +678,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       const bool has = lane < batch;
       const int32_t nid = has ? wq[tail - batch + lane] : 0;
       const NodeRec* nr = a.nodes + nid;
-      NodeLoad nd;
-      nd.l01 = *reinterpret_cast<const double2*>(&nr->lo[0]);
-      nd.l2h0 = *reinterpret_cast<const double2*>(&nr->lo[2]);
-      nd.h12 = *reinterpret_cast<const double2*>(&nr->hi[1]);
+      const NodeBox nd = load_node_box(nr);
       const int2 topo = *reinterpret_cast<const int2*>(&nr->first);
       const int32_t first = has ? topo.x : 0;
       // the node's tight box (its points' bounding box; it was pushed by its cell) against the
@@ -772,7 +718,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       const int incl = wave_incl_scan(nch, &tot);
       tail -= batch;  // the popped entries are in registers; pushes overwrite them
       if (tail + tot > kWideQueue) {
-        if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[34], 1ull);
+        if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_WIDE_STACK], 1ull);
         return false;
       }
       int off = tail + incl - nch;
@@ -784,7 +730,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
         wq[off++] = first + __builtin_popcount(meta & 0xffu & ((1u << o) - 1u));
       }
       tail += tot;
-      if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[5], 1ull);
+      if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_WALK_BATCHES], 1ull);
       wave_lds_fence();
       if (bm != 0) {
         seg(nleaf);
@@ -794,7 +740,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
         // a box this dense for its balls (their bounding box cuts a surface far wider than the
         // balls do) is left to the per-query searches, with the bounds found so far
         if (segs >= (have_prev ? kWideSegs : kWideSegs0) && tail > 0) {
-          if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[34], 1ull);
+          if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_WIDE_STACK], 1ull);
           return false;
         }
       }
@@ -804,9 +750,9 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       ++segs;
     }
     if (kDbg && a.dbg && lane == 0) {
-      atomicAdd(&a.dbg[32], 1ull);
-      atomicAdd(&a.dbg[33], (unsigned long long)segs);
-      atomicAdd(&a.dbg[36], (unsigned long long)listed);
+      atomicAdd(&a.dbg[ICP_DBG_WIDE_WAVES], 1ull);
+      atomicAdd(&a.dbg[ICP_DBG_WIDE_SEGMENTS], (unsigned long long)segs);
+      atomicAdd(&a.dbg[ICP_DBG_WIDE_POINTS], (unsigned long long)listed);
     }
     return true;
   };
@@ -863,15 +809,15 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
                        (funkey(wkh[2]) - funkey(wkl[2]));
       const float vmin = __int_as_float(__builtin_amdgcn_readlane((int)(unsigned)__double_as_longlong(hdr), 7));
       reuse = inside && vb >= vmin;
-      if (kDbg && a.dbg && lane == 0 && !reuse) atomicAdd(&a.dbg[inside ? 25 : 24], 1ull);
+      if (kDbg && a.dbg && lane == 0 && !reuse) atomicAdd(&a.dbg[inside ? ICP_DBG_WALK_LOOSE : ICP_DBG_WALK_MOVED], 1ull);
     }
     if (reuse) {
       nleaf = __builtin_amdgcn_readlane((int)(unsigned)__double_as_longlong(hdr), 6);
       // the frame is o: the reduction's offsets are the scan's, its group boxes the scan's
       ext = (double)pext * (1.0 + 0x1p-20);
       if (kDbg && a.dbg && lane == 0) {
-        atomicAdd(&a.dbg[12], 1ull);
-        atomicAdd(&a.dbg[17], (unsigned long long)nleaf);  // entries a reusing wave streams
+        atomicAdd(&a.dbg[ICP_DBG_CACHE_HITS], 1ull);
+        atomicAdd(&a.dbg[ICP_DBG_REUSED_ENTRIES], (unsigned long long)nleaf);  // entries a reusing wave streams
       }
     } else {
       // B in fp64: o + the wave's bounds, rounded outwards
@@ -970,7 +916,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       wb->gen = a.wc_gen;
       wb->vmin = (float)((whx - wlx) * (why - wly) * (whz - wlz) / a.wc_loose);
     }
-    if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[13], 1ull);
+    if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_CACHE_STORES], 1ull);
   };
   // An overflowing wave (its box holds more candidates than the list takes): its joined queries
   // are searched again as two 32-query halves (k_nn_half), each with the smaller box of its own
@@ -994,7 +940,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
           a.fb_list3[2 * at] = (int32_t)(2 * wid + 1);
           a.fb_list3[2 * at + 1] = (int32_t)(uint32_t)(dm >> 32);
         }
-        if (kDbg && a.dbg) atomicAdd(&a.dbg[16], (unsigned long long)nh);
+        if (kDbg && a.dbg) atomicAdd(&a.dbg[ICP_DBG_HALVES], (unsigned long long)nh);
       }
     } else if (!WIDE && a.fb_list4 != nullptr) {
       // the wide pass (k_nn_wide) searches the joined lanes again with the same box, walked and
@@ -1015,8 +961,8 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
     join = false;
   }
   if (kDbg && a.dbg && lane == 0) {
-    atomicAdd(&a.dbg[0], 1ull);
-    if (overflow) atomicAdd(&a.dbg[1], 1ull);
+    atomicAdd(&a.dbg[ICP_DBG_WAVES], 1ull);
+    if (overflow) atomicAdd(&a.dbg[ICP_DBG_OVERFLOW], 1ull);
   }
 
   PCLK(t_p3);
@@ -1195,9 +1141,9 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
           const float k1_in = k1;
           const int mp = len >> 1;
           if (kDbg && a.dbg && lane == 0) {
-            atomicAdd(&a.dbg[9], (unsigned long long)(maxc - r0 < SP ? maxc - r0 : SP));
-            atomicAdd(&a.dbg[10], (unsigned long long)mp);
-            atomicAdd(&a.dbg[11], 1ull);
+            atomicAdd(&a.dbg[ICP_DBG_STAGED], (unsigned long long)(maxc - r0 < SP ? maxc - r0 : SP));
+            atomicAdd(&a.dbg[ICP_DBG_SCAN_PAIRS], (unsigned long long)mp);
+            atomicAdd(&a.dbg[ICP_DBG_SCAN_ROUNDS], 1ull);
           }
 #pragma unroll 1
           for (int k = 0; k < mp; k++) eval2(st4[kStep * k], st4[kStep * k + 1], 2u * k);
@@ -1253,9 +1199,9 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
           const float k1_in = k1;
           const int mp = len >> 1;
           if (kDbg && a.dbg && lane == 0) {
-            atomicAdd(&a.dbg[9], (unsigned long long)maxf);
-            atomicAdd(&a.dbg[10], (unsigned long long)mp);
-            atomicAdd(&a.dbg[11], 1ull);
+            atomicAdd(&a.dbg[ICP_DBG_STAGED], (unsigned long long)maxf);
+            atomicAdd(&a.dbg[ICP_DBG_SCAN_PAIRS], (unsigned long long)mp);
+            atomicAdd(&a.dbg[ICP_DBG_SCAN_ROUNDS], 1ull);
           }
 #pragma unroll 1
           for (int k = 0; k < mp; k++) {
@@ -1309,49 +1255,47 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       } else {
         int wcount = 0;  // entries stored to the cache (points inside B+)
         auto gather_scan = [&](const int np) {
-        seg_n = np;
-        double4 nxtp = make_double4(0.0, 0.0, 0.0, 0.0);
-        if (lane < np) nxtp = load_cand(a.pts, plist[lane]);
-        for (int base = 0; base < np; base += 64) {
-          // a copy of an earlier point is staged far outside every group box (never scanned)
-          const bool cp = __double_as_longlong(nxtp.w) < 0;
-          const float vx = cp ? 0x1p62f : (float)(nxtp.x - ocx), vy = cp ? 0x1p62f : (float)(nxtp.y - ocy),
-                      vz = cp ? 0x1p62f : (float)(nxtp.z - ocz);
-          const float vw = __int_as_float((int)__double_as_longlong(nxtp.w));
-          if (wstore) {
-            const bool inp = base + lane < np && !cp && nxtp.x >= wlx && nxtp.x <= whx && nxtp.y >= wly &&
-                             nxtp.y <= why && nxtp.z >= wlz && nxtp.z <= whz;
-            const unsigned long long pm = wballot(inp);
-            if (inp) wents[wcount + mask_rank(pm)] = make_float4(vx, vy, vz, vw);
-            wcount += __popcll(pm);
+          seg_n = np;
+          double4 nxtp = make_double4(0.0, 0.0, 0.0, 0.0);
+          if (lane < np) nxtp = load_cand(a.pts, plist[lane]);
+          for (int base = 0; base < np; base += 64) {
+            // a copy of an earlier point is staged far outside every group box (never scanned)
+            const bool cp = __double_as_longlong(nxtp.w) < 0;
+            const float vx = cp ? 0x1p62f : (float)(nxtp.x - ocx), vy = cp ? 0x1p62f : (float)(nxtp.y - ocy),
+                        vz = cp ? 0x1p62f : (float)(nxtp.z - ocz);
+            const float vw = __int_as_float((int)__double_as_longlong(nxtp.w));
+            if (wstore) {
+              const bool inp = base + lane < np && !cp && nxtp.x >= wlx && nxtp.x <= whx && nxtp.y >= wly &&
+                               nxtp.y <= why && nxtp.z >= wlz && nxtp.z <= whz;
+              const unsigned long long pm = wballot(inp);
+              if (inp) wents[wcount + mask_rank(pm)] = make_float4(vx, vy, vz, vw);
+              wcount += __popcll(pm);
+            }
+            chunk(base, vx, vy, vz, vw, [&]() {
+              const int nb = base + 64;
+              if (nb + lane < np) nxtp = load_cand(a.pts, plist[nb + lane]);
+            });
           }
-          chunk(base, vx, vy, vz, vw, [&]() {
-            const int nb = base + 64;
-            if (nb + lane < np) nxtp = load_cand(a.pts, plist[nb + lane]);
-          });
-        }
-        if constexpr (WIDE) {
-          // The lane's winner so far is a point: its fl(d2) bounds the nearest one's. The balls
-          // shrink to the tighter bounds, and the box (in the same frame, rounded outwards) and
-          // the group boxes with them: every point of a final ball lies in every earlier box, so
-          // it is still listed and scanned; the rest of the walk visits less.
-          if (join && p1 >= 0) {
-            const TgtPt* p = a.pts + p1;
-            const double dx = p->x - qx, dy = p->y - qy, dz = p->z - qz;
-            const double d2 = dx * dx + dy * dy + dz * dz;
-            u = d2 < u ? d2 : u;
+          if constexpr (WIDE) {
+            // The lane's winner so far is a point: its fl(d2) bounds the nearest one's. The balls
+            // shrink to the tighter bounds, and the box (in the same frame, rounded outwards) and
+            // the group boxes with them: every point of a final ball lies in every earlier box, so
+            // it is still listed and scanned; the rest of the walk visits less.
+            if (join && p1 >= 0) {
+              const double d2 = d2_to_s(a.pts + p1, qx, qy, qz);
+              u = d2 < u ? d2 : u;
+            }
+            r = join ? ball_radius32(u, amax) : 0.f;
+            reduce((float)(qx - ocx), (float)(qy - ocy), (float)(qz - ocz));
+            blx = uniform_d(box_lo(ocx, funkey(wkl[0])));
+            bly = uniform_d(box_lo(ocy, funkey(wkl[1])));
+            blz = uniform_d(box_lo(ocz, funkey(wkl[2])));
+            bhx = uniform_d(box_hi(ocx, funkey(wkh[0])));
+            bhy = uniform_d(box_hi(ocy, funkey(wkh[1])));
+            bhz = uniform_d(box_hi(ocz, funkey(wkh[2])));
+            group_bounds((float)(ext * 0x1p-20));
+            group_spheres();
           }
-          r = join ? ball_radius32(u, amax) : 0.f;
-          reduce((float)(qx - ocx), (float)(qy - ocy), (float)(qz - ocz));
-          blx = uniform_d(box_lo(ocx, funkey(wkl[0])));
-          bly = uniform_d(box_lo(ocy, funkey(wkl[1])));
-          blz = uniform_d(box_lo(ocz, funkey(wkl[2])));
-          bhx = uniform_d(box_hi(ocx, funkey(wkh[0])));
-          bhy = uniform_d(box_hi(ocy, funkey(wkh[1])));
-          bhz = uniform_d(box_hi(ocz, funkey(wkh[2])));
-          group_bounds((float)(ext * 0x1p-20));
-          group_spheres();
-        }
         };
         if constexpr (WIDE) {
           // B itself (fp64, rounded outwards) in segments; a stack overflow leaves every joined
@@ -1366,7 +1310,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
           wstore = false;
         }
       }
-      if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[26], (unsigned long long)scanned_pts);  // sum over groups
+      if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_GROUP_POINTS], (unsigned long long)scanned_pts);  // sum over groups
       const float s2 = __uint_as_float(__float_as_uint(k2) & ~63u);  // <= the second-smallest value
       // fp64 distance of the fp32 winner, exactly as the leaf scan computes it (octree.cpp:139-144)
       double b64 = __builtin_inf();
@@ -1389,7 +1333,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
         wide_lane = join && !dec;
         if (kDbg && a.dbg) {
           const unsigned long long um = wballot(wide_lane);
-          if (lane == 0) atomicAdd(&a.dbg[35], (unsigned long long)__popcll(um));
+          if (lane == 0) atomicAdd(&a.dbg[ICP_DBG_WIDE_UNDECIDED], (unsigned long long)__popcll(um));
         }
         best = dec ? b64 : __builtin_inf();
         second = lb2;
@@ -1410,7 +1354,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
     wstore = false;
   }
   if (need64) {
-    if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[8], 1ull);
+    if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_FP64_WAVES], 1ull);
     // Points outside B are farther than r from every joined lane (each ball lies in B), so
     // they can neither be a joined lane's nearest point nor sit in its certificate window.
     // Exact duplicates of the winner (identical coordinates) are not ties: they share its leaf
@@ -1496,17 +1440,17 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       store_header(wcount);
       wstore = false;
     }
-    if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[4], (unsigned long long)scanned_pts);
+    if (kDbg && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_RESCAN_POINTS], (unsigned long long)scanned_pts);
   }
   if (kDbg && a.dbg) {
     const unsigned long long ex = wballot(cand && !join && !overflow);
     const unsigned long long cov = wballot(join && !(best <= u));
     const unsigned long long nc = wballot(active && finite_q && !safe && !cand);
     if (lane == 0) {
-      atomicAdd(&a.dbg[2], (unsigned long long)__popcll(ex));
-      atomicAdd(&a.dbg[3], (unsigned long long)__popcll(cov));
-      atomicAdd(&a.dbg[6], (unsigned long long)__popcll(nc));
-      atomicAdd(&a.dbg[7], (unsigned long long)nleaf);
+      atomicAdd(&a.dbg[ICP_DBG_NOT_JOINED], (unsigned long long)__popcll(ex));
+      atomicAdd(&a.dbg[ICP_DBG_NOT_COVERED], (unsigned long long)__popcll(cov));
+      atomicAdd(&a.dbg[ICP_DBG_NO_GUESS], (unsigned long long)__popcll(nc));
+      atomicAdd(&a.dbg[ICP_DBG_CANDIDATES], (unsigned long long)nleaf);
     }
   }
 
@@ -1553,11 +1497,11 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
 #if ICP_PHASE_CLOCKS
   PCLK(t_p5);
   if (a.dbg && lane == 0) {
-    atomicAdd(&a.dbg[16], t_p1 - t_p0);
-    atomicAdd(&a.dbg[17], t_p2 - t_p1);
-    atomicAdd(&a.dbg[18], t_p3 - t_p2);
-    atomicAdd(&a.dbg[19], t_p4 - t_p3);
-    atomicAdd(&a.dbg[20], t_p5 - t_p4);
+    atomicAdd(&a.dbg[ICP_DBG_CLK_GUESS], t_p1 - t_p0);
+    atomicAdd(&a.dbg[ICP_DBG_CLK_BOX], t_p2 - t_p1);
+    atomicAdd(&a.dbg[ICP_DBG_CLK_WALK], t_p3 - t_p2);
+    atomicAdd(&a.dbg[ICP_DBG_CLK_SCAN], t_p4 - t_p3);
+    atomicAdd(&a.dbg[ICP_DBG_CLK_FINISH], t_p5 - t_p4);
   }
 #endif
 }
@@ -1642,732 +1586,78 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ICP_WI
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// The ball search: four queries per wave, one 16-lane group (a DPP row) each. The list's queries
-// are latency-bound walks of a few dependent rounds, so four in flight per wave hide four times
-// the latency of one. A group collects, breadth-first from the cell tables of the query's box,
-// every leaf whose box distance s <= u (1 + 2^-47) (a sphere test) and scans their points one per
-// lane. Leaves with s > u (1 + 2^-47) only hold points with fl(d2) > best (1 + 2^-48) (monotone
-// rounding), so nothing in the certificate window is missed. Certification as in the wave search
-// (best <= u and the window test). A query the group cannot decide (no usable guess, an
-// overflowing candidate set, or no certificate) is finished right there by the group's first lane:
-// the per-lane certified search, else the reference-order DFS (stack in the group's LDS).
-// Before that, the kernel's threads take the exact list the wave search left, one query each
-// (the reference-order DFS). One launch for all the follow-up searches.
-constexpr int kBallGroups = 4;
-constexpr int kBallGL = 64 / kBallGroups;  // lanes per query
-constexpr int kBallStack = 512;
-constexpr int kBallPoints = 1024;
-constexpr int kBallGStack = kBallStack / kBallGroups;
-constexpr int kBallGPoints = kBallPoints / kBallGroups;
-constexpr int kBallLdsBytes = kBallStack * 4 + kBallPoints * 4;
-
-// The reference-order DFS for query i (octree.cpp:128-184), its result written.
-__device__ __forceinline__ void exact_query(const NNLaunch& a, int64_t i, unsigned long long* st, int bs) {
-  const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
-  double best_d2 = a.init_best, visits = 0.0, scanned = 0.0;
-  int32_t best = -1;
-  exact_dfs<false>(a, qx, qy, qz, st, bs, best, best_d2, visits, scanned);
-  a.pos_out[i] = best >= 0 ? best : a.pos0;
-  a.dist_out[i] = best >= 0 ? __builtin_sqrt(best_d2) : residual_to(a.pts, a.pos0, qx, qy, qz);
+// The instances' compile-time choices from the launch's run-time values: f(std::bool_constant),
+// f(std::integral_constant<int, NG>) for the scan groups (1, 2 or 4; anything else launches nothing).
+template <class F>
+void with_flag(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
 }
-
-// The per-lane certified search for query i; a query it cannot certify gets the reference-order
-// DFS right away. budget > 0: a search that needs more node visits gives up (returns false, nothing
-// written: the wave-cooperative search takes it).
-// *found: the best fl(d2) it had found when it gave up (a point's: an upper bound for the next search).
-// u: an upper bound of the nearest fl(d2) (inf: none), the search's initial prune bound.
-__device__ __forceinline__ bool lane_query(const NNLaunch& a, int64_t i, unsigned long long* st, int bs,
-                                           int budget = 0, double* found = nullptr, double u = __builtin_inf()) {
-  const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
-  double best = __builtin_inf(), second = __builtin_inf();
-  int32_t bpos = -1;
-  const double thr0 = u <= 0x1p900 ? u * (1.0 + kFastPrune) : __builtin_inf();
-  if (!fast_dfs(a, qx, qy, qz, st, bs, best, second, bpos, budget, thr0)) {
-    if (found) *found = best;
-    return false;
+template <class F>
+hipError_t with_scan_groups(int ng, F&& f) {
+  switch (ng) {
+    case 1: f(std::integral_constant<int, 1>{}); return hipSuccess;
+    case 2: f(std::integral_constant<int, 2>{}); return hipSuccess;
+    case 4: f(std::integral_constant<int, 4>{}); return hipSuccess;
+    default: return hipErrorInvalidValue;
   }
-  if (certified(best, second, a.init_best)) {
-    a.pos_out[i] = bpos;
-    a.dist_out[i] = __builtin_sqrt(best);
-  } else {
-    exact_query(a, i, st, bs);
-    atomicAdd(a.fb_count + 3, 1u);  // a DFS finish of the ball search
-    if (a.dbg) atomicAdd(&a.dbg[38], 1ull);
-  }
-  return true;
 }
-
-// Node visits a per-lane follow-up search may take before the wave-cooperative search takes over.
-// A query far (relative to the local point spacing) from a dense surface needs every leaf whose
-// box comes within its nearest distance: on the scene workload's outliers (metres above a ground
-// sampled every few mm) up to ~30k visits of one lane, ~1 us of dependent loads each (the
-// reference's DFS needs as many: tools/scene_probe.py). A wave's queue runs its lanes' searches
-// together, so the longest one sets its time: the budget bounds that, and the cooperative search
-// (64 nodes a step) takes the rest. Measured (profiles/r21/ab_lane_budget.txt, scene 20/5): 768
-// -> 64 visits: 1M 320 -> 635 Mcorr/s, 10M 600 -> 677; config 4 and config 3 unchanged.
-#ifndef ICP_LANE_BUDGET
-#define ICP_LANE_BUDGET 64
-#endif
-constexpr int kLaneBudget = ICP_LANE_BUDGET;
-constexpr int kBBStack = 2048;  // the cooperative search's node stack (int32 in LDS), the last
-constexpr int kBBPts = 256;     // kBBPts entries of which hold a step's leaf points
-
-// The wave-cooperative certified search of one query (every lane of the wave): branch and bound
-// over the octree, up to 64 nodes per step (one per lane, LIFO), each node re-tested against the
-// prune bound thr = best (1 + 2^-47) of the wave's best so far (exact as fast_dfs: a node is
-// skipped only when its squared box distance s exceeds thr, so every point of the certificate
-// window is scanned), leaves scanned by their lane, the best reduced over the wave every step.
-// u: an upper bound of the query's nearest fl(d2) (inf: none). A frontier that outgrows the stack
-// (a far query under a loose bound: every node within the bound is live) is searched again from
-// the root with the best point found so far as the bound, which prunes the frontier to the nodes
-// within the nearest distance (up to kBBPasses times while the bound shrinks). Returns false when
-// it still overflows and 2 for a tie (nothing written either way: the caller runs the
-// reference-order DFS), 1 after writing the certified result.
-constexpr int kBBPasses = 4;
-constexpr int kBBDone = 1;
-__device__ __forceinline__ int wave_bb(const NNLaunch& a, int64_t i, double u, int32_t* stack, int lane) {
-  const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
-  double best = __builtin_inf(), second = __builtin_inf();
-  int32_t bpos = 0x7fffffff;
-  int32_t* plist = stack + (kBBStack - kBBPts);
-  double thr = (u <= 0x1p900) ? u * (1.0 + kFastPrune) : __builtin_inf();
-  int steps = 0, passes = 0;
-  bool over = false;
-  while (true) {
-    // a pass: every point it scans is counted once (best, second from this pass only)
-    best = __builtin_inf();
-    second = __builtin_inf();
-    bpos = 0x7fffffff;
-    const double thr0 = thr;
-    // the start nodes: the cell-table nodes of the box q +- sqrt(thr) (every point within the
-    // bound lies in it: the ball search's radius), else the root; the descent's levels skipped
-    int tail = 1;
-    if (a.cells && thr <= 0x1p900) {
-      const double amax = __builtin_fmax(__builtin_fabs(qx), __builtin_fmax(__builtin_fabs(qy), __builtin_fabs(qz)));
-      const double r = __builtin_sqrt(thr) * (1.0 + 0x1p-40) + amax * 0x1p-45;
-      tail = cell_starts<64, 2>(a, qx - r, qy - r, qz - r, qx + r, qy + r, qz + r, lane, 0, stack);
-    } else if (lane == 0) {
-      stack[0] = 0;
-    }
-    over = false;
-    ++passes;
-    wave_lds_fence();
-    while (tail > 0) {
-      const int batch = tail < 64 ? tail : 64;
-      const bool has = lane < batch;
-      const int32_t nid = has ? stack[tail - batch + lane] : 0;
-      tail -= batch;
-      const NodeRec* rr = a.nodes + nid;
-      const int2 topo = *reinterpret_cast<const int2*>(&rr->first);
-      const uint32_t meta = (uint32_t)topo.y;
-      // pushed against an older (larger) bound, and pushed by its cell: test the node's tight box
-      const float4 tb0 = *reinterpret_cast<const float4*>(&a.tbox[nid].lo[0]);
-      const float2 tb1 = *reinterpret_cast<const float2*>(&a.tbox[nid].hi[1]);
-      const bool live = has && !(box_s(tb0.x, tb0.y, tb0.z, tb0.w, tb1.x, tb1.y, qx, qy, qz) > thr);
-      const bool lf = live && (meta & kLeafBit);
-      const uint32_t kids = (live && !lf) ? children_in_ball(rr, meta & 0xffu, qx, qy, qz, thr) : 0u;
-      // The step's leaf points, flat: listed in LDS kBBPts at a time and scanned kBBPts / 64 per
-      // lane with all their loads in flight together (a leaf scanned by its own lane was ~10
-      // dependent round trips per step). Each point is scanned by one lane: the per-lane best and
-      // second reduce to the wave's exactly as before.
-      const int lcnt = lf ? (int)(meta & ~kLeafBit) : 0;
-      int ltot;
-      const int lfirst = wave_incl_scan(lcnt, &ltot) - lcnt;
-      for (int base = 0; base < ltot; base += kBBPts) {
-        for (int k = 0; k < lcnt; k++) {
-          const int f = lfirst + k - base;
-          if (f >= 0 && f < kBBPts) plist[f] = topo.x + k;
-        }
-        wave_lds_fence();
-        const int m = ltot - base < kBBPts ? ltot - base : kBBPts;
-        constexpr int P = kBBPts / 64;
-        double px[P], py[P], pz[P];
-        int32_t pid[P];
-#pragma unroll
-        for (int t = 0; t < P; t++) {
-          pid[t] = t * 64 + lane < m ? plist[t * 64 + lane] : -1;
-          const TgtPt* p = a.pts + (pid[t] >= 0 ? pid[t] : 0);
-          const double2 pxy = *reinterpret_cast<const double2*>(&p->x);
-          const double2 pzw = *reinterpret_cast<const double2*>(&p->z);
-          px[t] = pxy.x;
-          py[t] = pxy.y;
-          pz[t] = pzw.x;
-          pid[t] = tgt_copy_word(pzw.y) ? -1 : pid[t];  // a copy: its earlier twin is scanned
-        }
-#pragma unroll
-        for (int t = 0; t < P; t++) {
-          const double dx = px[t] - qx, dy = py[t] - qy, dz = pz[t] - qz;
-          const double d2 = dx * dx + dy * dy + dz * dz;
-          if (pid[t] >= 0) {
-            if (d2 < best) {
-              second = best;
-              best = d2;
-              bpos = pid[t];
-            } else if (d2 < second) {
-              second = d2;
-            }
-          }
-        }
-        wave_lds_fence();  // the list's reads are done before the next round rewrites it
-      }
-      const int nch = __builtin_popcount(kids);
-      int tot;
-      const int incl = wave_incl_scan(nch, &tot);
-      if (tail + tot > kBBStack - kBBPts) {
-        over = true;
-        break;
-      }
-      wave_lds_fence();  // this step's pops are read before the pushes overwrite them
-      int off = tail + incl - nch;
-      uint32_t kk = kids;
-      while (kk) {
-        const uint32_t o = (uint32_t)__builtin_ctz(kk);
-        kk &= kk - 1u;
-        stack[off++] = topo.x + __builtin_popcount((meta & 0xffu) & ((1u << o) - 1u));
-      }
-      tail += tot;
-      const double gb = wave_min_d(best);
-      const double t2 = gb * (1.0 + kFastPrune);
-      thr = t2 < thr ? t2 : thr;
-      ++steps;
-      wave_lds_fence();
-    }
-    wave_lds_fence();
-    // again with the tighter bound (thr holds the best so far), while it shrinks
-    if (!over || passes >= kBBPasses || !(thr < thr0)) break;
-  }
-  if (a.dbg && lane == 0) {
-    atomicAdd(&a.dbg[27], 1ull);
-    atomicAdd(&a.dbg[28], (unsigned long long)steps);
-    if (over) atomicAdd(&a.dbg[37], 1ull);
-  }
-  if (over) return 0;
-  // the wave's best, and its second: the smallest of the other lanes' bests and the best lane's
-  // second (a best held by two lanes is its own second: a tie)
-  const double gb = wave_min_d(best);
-  const unsigned long long at = wballot(best == gb);
-  const double gs = __popcll(at) > 1 ? gb : wave_min_d(best == gb ? second : best);
-  const int32_t gp = (int32_t)__builtin_amdgcn_readlane(bpos, __builtin_ctzll(at ? at : 1ull));
-  if (!certified(gb, gs, a.init_best)) return 2;
-  if (lane == 0) {
-    a.pos_out[i] = gp;
-    a.dist_out[i] = __builtin_sqrt(gb);
-  }
-  return kBBDone;
-}
-
-__global__ void __launch_bounds__(64) k_nn_ball(NNLaunch a) {
-  if (a.loop && a.loop->core.done) return;
-  extern __shared__ __attribute__((aligned(16))) unsigned long long lds_raw[];
-  const int lane = threadIdx.x, g = lane / kBallGL, gl = lane % kBallGL, gbase = g * kBallGL;
-  int32_t* stack = reinterpret_cast<int32_t*>(lds_raw) + g * kBallGStack;
-  int32_t* plist = reinterpret_cast<int32_t*>(lds_raw) + kBallStack + g * kBallGPoints;
-  // The exact list (queries the wave search could not certify): complete when this kernel starts,
-  // one thread each, a DFS stack of `levels` entries per thread in LDS.
-  {
-    const unsigned n0 = a.fb_count[0];
-    for (unsigned j = blockIdx.x * 64u + (unsigned)lane; j < n0; j += gridDim.x * 64u)
-      exact_query(a, a.fb_list[j], lds_raw + lane, 64);
-    wave_lds_fence();
-  }
-  // The follow-ups of the ball queries (a per-lane certified search, or the reference-order DFS)
-  // are queued per wave and run 64 at a time, one query per lane with its own DFS stack column
-  // (the exact list's layout), once the queue is nearly full and at the end. (One lane of the
-  // query's group ran each inline before: 1 lane in 16 busy. On a dense 2.5-D scan early in a
-  // registration the queries sit ~0.3 m off surfaces sampled every few mm, every ball overflows,
-  // and that serial tail took 21 ms per iterate at 1M points.)
-  int32_t* fq = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(lds_raw) + a.ball_queue_off);
-  double* fqu = reinterpret_cast<double*>(fq + 64);  // each entry's guess u (an upper bound, or inf)
-  int qn = 0;  // wave-uniform
-  // A per-lane search that exceeds kLaneBudget node visits is handed to the wave-cooperative
-  // search (the whole wave on one query), one after the other once the lanes are done.
-  auto flush = [&]() {
-    wave_lds_fence();
-    bool handed = false;
-    int32_t e = 0;
-    double qu = __builtin_inf();
-    if (lane < qn) {
-      e = fq[lane];
-      qu = fqu[lane];
-      const int64_t iq = e & 0x3fffffff;
-      // an abandoned search's best so far (a point's fl(d2)) bounds the cooperative search
-      double found = __builtin_inf();
-      if ((e >> 30) == 1) handed = !lane_query(a, iq, lds_raw + lane, 64, kLaneBudget, &found, qu);
-      else exact_query(a, iq, lds_raw + lane, 64);
-      qu = found < qu ? found : qu;
-    }
-    wave_lds_fence();
-    const unsigned long long handed_m = wballot(handed);
-    if (a.dbg && lane == 0) atomicAdd(&a.dbg[29], (unsigned long long)__popcll(handed_m));
-    for (unsigned long long hm = wballot(handed); hm; hm &= hm - 1) {
-      const int k = __builtin_ctzll(hm);
-      const int64_t iq = __builtin_amdgcn_readlane(e, k) & 0x3fffffff;
-      const double uq = readlane_d(qu, k);
-      // the stack in the DFS columns' area (free now); the fallback DFS after it, in the same area
-      // the stack in the DFS columns' area (free now); a tie or an overflow: the reference-order
-      // DFS on lane 0, in the same area
-      if (wave_bb(a, iq, uq, reinterpret_cast<int32_t*>(lds_raw), lane) != kBBDone && lane == 0) {
-        exact_query(a, iq, lds_raw, 1);
-        atomicAdd(a.fb_count + 3, 1u);
-        if (a.dbg) atomicAdd(&a.dbg[38], 1ull);
-      }
-      wave_lds_fence();
-    }
-    qn = 0;
-    wave_lds_fence();
-  };
-  const unsigned cnt = a.fb_count[1];
-  // Direct mode: each wave takes whole queries, one after the other, with all its lanes: the
-  // cooperative search started from the cell tables of the query's bound (a few 64-node steps
-  // instead of the 16-lane ball walk and the follow-ups after it). Used for a long list (over four
-  // per wave: an unconverged registration on surface data, where most balls overflow) and after
-  // the wide pass; the four-queries-per-wave ball walk takes the shorter lists, whose queries are
-  // mostly easy. (Short lists, at most one query per wave, went to the direct mode too until r23:
-  // since the flat leaf scans of r22 the ball walk settles them faster, config 3 6.2k -> 7.4k,
-  // config 2 1.35k -> 1.41k Mcorr/s, profiles/r23/ab_ball_mode_configs23.txt.) Measured (profiles/r21/ab_ball_direct.txt): scene 10M 678 -> 1215 Mcorr/s,
-  // scene 1M 624 -> 1254 (driver window), config 4 unchanged; direct at every size cost config
-  // 4's window 4 % (its 15k-query lists of easy balls).
-  // (icp_hip_config.ball_mode: 0 this rule, 1 the ball walk always, 2 direct always)
-  if (a.ball_mode == 2 || (a.ball_mode == 0 && cnt > 4u * gridDim.x)) {
-    // A query the cooperative search leaves (a tie, an overflow) is queued for the reference-order
-    // DFS; the queue runs 64 at a time, one per lane, each with its DFS stack column in LDS (ties
-    // come in numbers where both clouds sit on the LAS grid: the source's first iterate)
-    unsigned taken = 0;
-    int dq = 0;  // wave-uniform
-    auto dfs_flush = [&]() {
-      wave_lds_fence();
-      if (lane < dq) exact_query(a, fq[lane], lds_raw + lane, 64);
-      if (lane == 0) {
-        atomicAdd(a.fb_count + 3, (unsigned)dq);
-        if (a.dbg) atomicAdd(&a.dbg[38], (unsigned long long)dq);
-      }
-      dq = 0;
-      wave_lds_fence();
-    };
-    for (unsigned j = blockIdx.x; j < cnt; j += gridDim.x, ++taken) {
-      const int64_t i = a.fb_list2[j];
-      const double u = a.fb_u2[j];
-      if (wave_bb(a, i, u, reinterpret_cast<int32_t*>(lds_raw), lane) != kBBDone) {
-        wave_lds_fence();
-        if (lane == 0) fq[dq] = (int32_t)i;
-        if (++dq == 64) dfs_flush();
-      }
-      wave_lds_fence();
-    }
-    if (dq > 0) dfs_flush();
-    // the queries taken by the cooperative search count as follow-up searches, as after the ball
-    // walk (icp_iter_stats.n_lane_search)
-    if (lane == 0 && taken > 0) atomicAdd(a.fb_count + 2, taken);
-    return;
-  }
-  for (unsigned j0 = blockIdx.x * kBallGroups; j0 < cnt; j0 += gridDim.x * kBallGroups) {
-    const unsigned j = j0 + g;
-    bool live = j < cnt;  // group-uniform
-    int follow = 0;       // group-uniform: 1 the per-lane search, 2 the reference-order DFS
-    int64_t i = 0;
-    double u = 0.0, qx = 0.0, qy = 0.0, qz = 0.0;
-    if (live) {
-      i = a.fb_list2[j];
-      u = a.fb_u2[j];
-      qx = a.x[i];
-      qy = a.y[i];
-      qz = a.z[i];
-      if (!(u <= 0x1p900)) {
-        follow = 1;
-        live = false;
-      }
-    }
-    const double thr = u * (1.0 + kFastPrune);
-    int tail = 0, npts = 0;
-    bool overflow = false;
-    wave_lds_fence();
-    {
-      // every point with fl(d2) <= thr lies in the box q +- r (see the wave search's radius)
-      const double amax = __builtin_fmax(__builtin_fabs(qx), __builtin_fmax(__builtin_fabs(qy), __builtin_fabs(qz)));
-      const double r = live ? __builtin_sqrt(thr) * (1.0 + 0x1p-40) + amax * 0x1p-45 : 0.0;
-      if (a.cells) {
-        const int t = cell_starts<kBallGL, 1>(a, qx - r, qy - r, qz - r, qx + r, qy + r, qz + r, gl, gbase, stack);
-        tail = live ? t : 0;
-      } else {
-        if (gl == 0) stack[0] = 0;
-        tail = live ? 1 : 0;
-      }
-    }
-    wave_lds_fence();
-    // LIFO batches of up to 16 nodes per group, sphere test s <= thr on the children
-    while (wballot(tail > 0) != 0) {
-      const int batch = tail < kBallGL ? tail : kBallGL;
-      const bool has = gl < batch;
-      bool leaf = false;
-      int32_t first = 0;
-      uint32_t meta = 0, kids = 0;
-      if (has) {
-        const NodeRec* rr = a.nodes + stack[tail - batch + gl];
-        const int2 topo = *reinterpret_cast<const int2*>(&rr->first);
-        first = topo.x;
-        meta = (uint32_t)topo.y;
-        leaf = (meta & kLeafBit) != 0;
-        if (!leaf) kids = children_in_ball(rr, meta & 0xffu, qx, qy, qz, thr);
-      }
-      const int lcnt = (has && leaf) ? (int)(meta & ~kLeafBit) : 0;
-      int ltot;
-      const int lincl = row_incl_scan(lcnt, gbase, &ltot);
-      const int lpos = npts + lincl - lcnt;
-      if (lcnt > 0 && lpos + lcnt <= kBallGPoints)
-        for (int c = 0; c < lcnt; c++) plist[lpos + c] = first + c;
-      const int nch = __builtin_popcount(kids);
-      int tot;
-      const int incl = row_incl_scan(nch, gbase, &tot);
-      if (tail > 0) {
-        npts += ltot;
-        tail -= batch;
-        if (npts > kBallGPoints || tail + tot > kBallGStack) {
-          overflow = true;
-          tail = 0;
-        } else {
-          int off = tail + incl - nch;
-          const uint32_t mask = meta & 0xffu;
-          uint32_t kk = kids;
-          while (kk) {
-            const uint32_t o = (uint32_t)__builtin_ctz(kk);
-            kk &= kk - 1u;
-            stack[off++] = first + __builtin_popcount(mask & ((1u << o) - 1u));
-          }
-          tail += tot;
-        }
-      }
-      wave_lds_fence();
-    }
-    if (a.dbg && gl == 0 && live) {
-      atomicAdd(&a.dbg[14], overflow ? 1ull : 0ull);
-      atomicAdd(&a.dbg[15], (unsigned long long)npts);
-    }
-    if (live && overflow) follow = 1;
-    if (overflow) live = false;
-    wave_lds_fence();
-    double best = __builtin_inf(), second = __builtin_inf();
-    int32_t bpos = 0x7fffffff;
-    if (live) {
-      for (int k = gl; k < npts; k += kBallGL) {
-        const int32_t pg = plist[k];
-        const TgtPt* p = a.pts + pg;
-        const double2 xy = *reinterpret_cast<const double2*>(&p->x);
-        const double dx = xy.x - qx, dy = xy.y - qy, dz = p->z - qz;
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        if (d2 < best) {
-          second = best;
-          best = d2;
-          bpos = pg;
-        } else if (d2 < second) {
-          second = d2;
-        }
-      }
-    }
-#pragma unroll
-    for (int o = kBallGL / 2; o >= 1; o >>= 1) {
-      const double ob = __shfl_xor(best, o, kWave);
-      const double os = __shfl_xor(second, o, kWave);
-      const int32_t op = __shfl_xor(bpos, o, kWave);
-      const double lo_ = ob < best ? ob : best;
-      const double hi_ = ob < best ? best : ob;
-      const double ss = os < second ? os : second;
-      second = hi_ < ss ? hi_ : ss;
-      bpos = (ob < best || (ob == best && op < bpos)) ? op : bpos;
-      best = lo_;
-    }
-    if (live) {
-      if (!(best <= u)) {
-        follow = 1;
-      } else if (certified(best, second, a.init_best)) {
-        if (gl == 0) {
-          a.pos_out[i] = bpos;
-          a.dist_out[i] = __builtin_sqrt(best);
-        }
-      } else {
-        follow = 2;
-      }
-    }
-    // queue the follow-ups (one entry per group: its leader lane)
-    const bool fol = follow != 0 && gl == 0;
-    const unsigned long long fm = wballot(fol);
-    if (fol) {
-      atomicAdd(a.fb_count + (follow == 1 ? 2 : 3), 1u);  // counted for the iteration record
-      fq[qn + mask_rank(fm)] = (int32_t)i | (follow << 30);
-      // an overflowing ball's guess bounds the nearest distance (a guess the ball did not cover
-      // does not, nor does an unusable one)
-      fqu[qn + mask_rank(fm)] = (overflow && u <= 0x1p900) ? u : __builtin_inf();
-    }
-    qn += __popcll(fm);
-    if (qn > 64 - kBallGroups) flush();
-    wave_lds_fence();
-  }
-  if (qn > 0) flush();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Separation of the target points (once per target): for every point p_j a lower bound S_j of its
-// exact distance to every OTHER target point, stored in TgtPt::sep (fp32, rounded down; 0 when
-// p_j has an exact duplicate). It turns the previous match into a certificate (k_nn_wave,
-// icp_hip_config.certify_prev): a moved query q' with exact distance D* to its previous match p*
-// has D(q', p) >= S - D* for every other point p (triangle inequality), so p* is the nearest with
-// the reference's own certificate (nn_device.h) whenever (S - D*)^2 clears fl(d2(q', p*)) by the
-// window. One thread per point (leaf order: neighbours in flight together), a branch-and-bound
-// DFS for the nearest point other than itself: nearest child first, the remaining siblings of a
-// level kept as one stack entry with a 16-bit lower-bound key (fast_dfs's encoding); a node is
-// skipped when its squared box distance s exceeds the best (monotone rounding: every point inside
-// has fl(d2) >= s), so the result is the exact minimum fl(d2) over the other points.
-__global__ void __launch_bounds__(256) k_target_sep(const NodeRec* __restrict__ nodes, TgtPt* __restrict__ pts,
-                                                    int64_t n) {
-  extern __shared__ __attribute__((aligned(16))) unsigned long long sep_stack[];
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;  // no barriers below
-  unsigned long long* st = sep_stack + threadIdx.x;
-  const int bs = blockDim.x;
-  const double2 qxy = *reinterpret_cast<const double2*>(&pts[j].x);
-  const double qx = qxy.x, qy = qxy.y, qz = pts[j].z;
-  double best = __builtin_inf();
-  uint32_t thr_key = key16(best);
-  int sp = 0;
-  int32_t node = 0;
-  double lx = nodes[0].lo[0], ly = nodes[0].lo[1], lz = nodes[0].lo[2];
-  double hx = nodes[0].hi[0], hy = nodes[0].hi[1], hz = nodes[0].hi[2];
-  double s = box_s(lx, ly, lz, hx, hy, hz, qx, qy, qz);
-  while (true) {
-    bool entered = false;
-    if (!(s > best)) {
-      const int2 topo = *reinterpret_cast<const int2*>(&nodes[node].first);
-      const int32_t first = topo.x;
-      const uint32_t meta = (uint32_t)topo.y;
-      if (meta & kLeafBit) {
-        const int32_t cnt = (int32_t)(meta & ~kLeafBit);
-        for (int32_t k = 0; k < cnt; k++) {
-          if ((int64_t)first + k == j) continue;
-          const TgtPt* p = pts + first + k;
-          const double2 pxy = *reinterpret_cast<const double2*>(&p->x);
-          const double dx = pxy.x - qx, dy = pxy.y - qy, dz = p->z - qz;
-          const double d2 = dx * dx + dy * dy + dz * dz;
-          if (d2 < best) {
-            best = d2;
-            thr_key = key16(best);
-          }
-        }
-      } else {
-        const double mx = (lx + hx) / 2, my = (ly + hy) / 2, mz = (lz + hz) / 2;
-        const double ax0 = smax(0.0, smax(lx - qx, qx - mx)), ax1 = smax(0.0, smax(mx - qx, qx - hx));
-        const double ay0 = smax(0.0, smax(ly - qy, qy - my)), ay1 = smax(0.0, smax(my - qy, qy - hy));
-        const double az0 = smax(0.0, smax(lz - qz, qz - mz)), az1 = smax(0.0, smax(mz - qz, qz - hz));
-        const double sx[2] = {ax0 * ax0, ax1 * ax1};
-        const double sy[2] = {ay0 * ay0, ay1 * ay1};
-        const double sz[2] = {az0 * az0, az1 * az1};
-        const uint32_t mask = meta & 0xffu;
-        double bs_ = __builtin_inf();
-        uint32_t o1 = 0;
-#pragma unroll
-        for (int o = 0; o < 8; o++) {
-          const double c = sx[o & 1] + sy[(o >> 1) & 1] + sz[o >> 2];
-          const bool take = ((mask >> o) & 1u) && c < bs_;
-          bs_ = take ? c : bs_;
-          o1 = take ? (uint32_t)o : o1;
-        }
-        const uint32_t rem = mask & ~(1u << o1);
-        uint32_t kmin = 0xffffu;
-#pragma unroll
-        for (int o = 0; o < 8; o++) {
-          const double c = sx[o & 1] + sy[(o >> 1) & 1] + sz[o >> 2];
-          const uint32_t kk = key16(c);
-          kmin = ((rem >> o) & 1u) && kk < kmin ? kk : kmin;
-        }
-        if (rem) {
-          st[sp * bs] = ((unsigned long long)kmin << 48) | ((unsigned long long)mask << 40) |
-                        ((unsigned long long)rem << 32) | (uint32_t)first;
-          sp++;
-        }
-        node = first + __builtin_popcount(mask & ((1u << o1) - 1u));
-        if (o1 & 1u) lx = mx; else hx = mx;
-        if (o1 & 2u) ly = my; else hy = my;
-        if (o1 & 4u) lz = mz; else hz = mz;
-        s = bs_;
-        entered = true;
-      }
-    }
-    if (entered) continue;
-    bool found = false;
-    while (sp > 0) {
-      const unsigned long long e = st[(sp - 1) * bs];
-      if ((uint32_t)(e >> 48) > thr_key) {  // key16 is monotone: every remaining child has s > best
-        sp--;
-        continue;
-      }
-      uint32_t rem = (uint32_t)(e >> 32) & 0xffu;
-      const uint32_t pmask = (uint32_t)(e >> 40) & 0xffu;
-      const int32_t first = (int32_t)(uint32_t)e;
-      const uint32_t o = (uint32_t)__builtin_ctz(rem);
-      rem &= rem - 1u;
-      if (rem == 0) sp--;
-      else st[(sp - 1) * bs] = (e & ~(0xffull << 32)) | ((unsigned long long)rem << 32);
-      node = first + __builtin_popcount(pmask & ((1u << o) - 1u));
-      const NodeRec* r = nodes + node;
-      const double2 l01 = *reinterpret_cast<const double2*>(&r->lo[0]);
-      const double2 l2h0 = *reinterpret_cast<const double2*>(&r->lo[2]);
-      const double2 h12 = *reinterpret_cast<const double2*>(&r->hi[1]);
-      lx = l01.x; ly = l01.y; lz = l2h0.x; hx = l2h0.y; hy = h12.x; hz = h12.y;
-      s = box_s(lx, ly, lz, hx, hy, hz, qx, qy, qz);
-      found = true;
-      break;
-    }
-    if (!found) break;
-  }
-  // fl(d2) <= D^2 (1 + 5 2^-53), so D >= sqrt(best) (1 - 2^-50) (the fp64 sqrt within an ulp);
-  // the fp32 conversion rounds by <= 2^-24, covered by the 2^-22 factor: sep <= D
-  float sep = __builtin_inff();
-  if (best < __builtin_inf()) sep = (float)(__builtin_sqrt(best) * ((1.0 - 0x1p-50) * (1.0 - 0x1p-22)));
-  if (!(sep >= 0.0f)) sep = 0.0f;
-  pts[j].sep = sep;
-}
-
-inline unsigned grid_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 }  // namespace
 
-int nn_block_threads(int levels) {
-  // LDS stack of the per-thread kernels: levels x threads x 8 B. Keep <= 64 KiB per block.
-  if (levels <= 32) return 256;
-  if (levels <= 64) return 128;
-  return 64;
-}
-
-hipError_t launch_target_sep(const NodeRec* nodes, TgtPt* pts, int64_t n, int levels, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  const int lv = levels < 1 ? 1 : levels;
-  const int bs = nn_block_threads(lv);
-  const size_t shmem = (size_t)lv * bs * sizeof(unsigned long long);
-  hipLaunchKernelGGL(k_target_sep, dim3(grid_for(n, bs)), dim3(bs), shmem, s, nodes, pts, n);
-  return hipGetLastError();
-}
-
 hipError_t launch_nn(const NNLaunch& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  const int levels = a.levels < 1 ? 1 : a.levels;
-  const int bs = nn_block_threads(levels);
-  size_t shmem = (size_t)levels * bs * sizeof(unsigned long long);
-  if (shmem < 1024) shmem = 1024;  // also hosts the block reduction
-  const unsigned grid = grid_for(a.n, bs);
-  if (a.search == ICP_SEARCH_REFERENCE || a.count) {
-    if (a.ev_start) (void)hipEventRecord(a.ev_start, s);
-    if (a.apply) {
-      if (a.count) hipLaunchKernelGGL((k_nn_ref<true, true>), dim3(grid), dim3(bs), shmem, s, a);
-      else hipLaunchKernelGGL((k_nn_ref<true, false>), dim3(grid), dim3(bs), shmem, s, a);
-    } else {
-      if (a.count) hipLaunchKernelGGL((k_nn_ref<false, true>), dim3(grid), dim3(bs), shmem, s, a);
-      else hipLaunchKernelGGL((k_nn_ref<false, false>), dim3(grid), dim3(bs), shmem, s, a);
-    }
-    if (a.ev_fast_done) (void)hipEventRecord(a.ev_fast_done, s);
-    return hipGetLastError();
-  }
+  if (a.search == ICP_SEARCH_REFERENCE || a.count) return launch_nn_ref(a, s);
   // wave search -> ball search -> per-lane search / exact DFS
-  const unsigned wgrid = grid_for(a.n, 256);
+  const unsigned wgrid = (unsigned)((a.n + 255) / 256);
   const size_t wshm = (size_t)(256 / 64) * kWaveLds;
-  // The timing events ride on the search's own dispatch packet (no marker packets between
-  // kernels). An event on a dispatch delays the next kernel by ~3-5 us (its start event carried
-  // by the next kernel's dispatch instead measured no better), so the context times only every
-  // config.timing_stride-th iterate (null events: plain launches).
-  auto wave = [&](auto kern) {
-    hipExtLaunchKernelGGL(kern, dim3(wgrid), dim3(256), (uint32_t)wshm, s, a.ev_start, a.ev_fast_done, 0u, a);
-  };
+  // The second passes search queries that are already moved: no transform, no cache. About one
+  // resident block per slot.
+  NNLaunch h = a;
+  h.apply = 0;
+  h.wc_box = nullptr;
+  h.wc_ents = nullptr;
+  const int64_t hb = ((a.n + 31) / 32 + 3) / 4, wb = (a.n + 255) / 256;
+  const unsigned hgrid = (unsigned)(hb < 2048 ? hb : 2048), ggrid = (unsigned)(wb < 2048 ? wb : 2048);
+  const size_t gshm = (size_t)(256 / 64) * kWideLds;
   // the previous-match certificate only where it can apply (an iterate after a search)
   const bool cert = a.certify_prev != 0 && a.have_prev;
-  // instances: transform, scan groups, certificate, debug counters
-  auto pick = [&](auto cert_c, auto dbg_c) -> hipError_t {
-    constexpr bool C = decltype(cert_c)::value, D = decltype(dbg_c)::value;
-    // the cache instance where every joined wave reuses or stores (an iterate after a search)
-    const bool wc = ICP_WALK_STREAM && a.apply && a.wc_box != nullptr && a.have_prev;
-    // the instance without the cache for a source's first iterate (its walking waves store
-    // nothing; a record is reused only after a search)
-    const bool nc = ICP_FIRST_NC && !a.apply && !a.have_prev;
-    switch ((wc ? 16 : 0) + (nc ? 32 : 0) + (a.apply ? 8 : 0) + a.scan_groups) {
-      case 25: wave(k_nn_wave<true, 1, C, D, 1>); break;
-      case 26: wave(k_nn_wave<true, 2, C, D, 1>); break;
-      case 28: wave(k_nn_wave<true, 4, C, D, 1>); break;
-      case 9: wave(k_nn_wave<true, 1, C, D, 0>); break;
-      case 10: wave(k_nn_wave<true, 2, C, D, 0>); break;
-      case 12: wave(k_nn_wave<true, 4, C, D, 0>); break;
-      case 33: wave(k_nn_wave<false, 1, C, D, 2>); break;
-      case 34: wave(k_nn_wave<false, 2, C, D, 2>); break;
-      case 36: wave(k_nn_wave<false, 4, C, D, 2>); break;
-      case 1: wave(k_nn_wave<false, 1, C, D, 0>); break;
-      case 2: wave(k_nn_wave<false, 2, C, D, 0>); break;
-      case 4: wave(k_nn_wave<false, 4, C, D, 0>); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipSuccess;
-  };
-  using T_ = std::true_type;
-  using F_ = std::false_type;
-  const bool dbg = a.dbg != nullptr;
-  const hipError_t pe = cert ? (dbg ? pick(T_{}, T_{}) : pick(T_{}, F_{})) : (dbg ? pick(F_{}, T_{}) : pick(F_{}, F_{}));
+  // the cache instance where every joined wave reuses or stores (an iterate after a search)
+  const bool wc = ICP_WALK_STREAM && a.apply && a.wc_box != nullptr && a.have_prev;
+  // the instance without the cache for a source's first iterate (its walking waves store
+  // nothing; a record is reused only after a search)
+  const bool nc = ICP_FIRST_NC && !a.apply && !a.have_prev;
+  // instances: transform, scan groups, certificate, debug counters, cache
+  const hipError_t pe = with_scan_groups(a.scan_groups, [&](auto ng_c) {
+    with_flag(a.dbg != nullptr, [&](auto dbg_c) {
+      constexpr int G = decltype(ng_c)::value;
+      constexpr bool D = decltype(dbg_c)::value;
+      // The timing events ride on the search's own dispatch packet (no marker packets between
+      // kernels). An event on a dispatch delays the next kernel by ~3-5 us (its start event carried
+      // by the next kernel's dispatch instead measured no better), so the context times only every
+      // config.timing_stride-th iterate (null events: plain launches).
+      auto wave = [&](auto kern) {
+        hipExtLaunchKernelGGL(kern, dim3(wgrid), dim3(256), (uint32_t)wshm, s, a.ev_start, a.ev_fast_done, 0u, a);
+      };
+      with_flag(cert, [&](auto cert_c) {
+        constexpr bool C = decltype(cert_c)::value;
+        if (wc) wave(k_nn_wave<true, G, C, D, 1>);
+        else if (nc) wave(k_nn_wave<false, G, C, D, 2>);
+        else if (a.apply) wave(k_nn_wave<true, G, C, D, 0>);
+        else wave(k_nn_wave<false, G, C, D, 0>);
+      });
+      // the half pass over the overflowed waves
+      if (a.fb_list3)
+        hipExtLaunchKernelGGL((k_nn_half<G, D>), dim3(hgrid), dim3(256), (uint32_t)wshm, s, nullptr, nullptr, 0u, h);
+      // the wide pass over the overflowed waves and halves
+      if (a.fb_list4)
+        hipExtLaunchKernelGGL((k_nn_wide<G, D>), dim3(ggrid), dim3(256), (uint32_t)gshm, s, nullptr, nullptr, 0u, h);
+    });
+  });
   if (pe != hipSuccess) return pe;
-  // the half pass over the overflowed waves (queries already moved: no transform, no cache)
-  if (a.fb_list3) {
-    NNLaunch h = a;
-    h.apply = 0;
-    h.wc_box = nullptr;
-    h.wc_ents = nullptr;
-    const int64_t halves = (a.n + 31) / 32;
-    const int64_t hb = (halves + 3) / 4;
-    const unsigned hgrid = (unsigned)(hb < 2048 ? hb : 2048);  // about one resident block per slot
-    auto half = [&](auto kern) {
-      hipExtLaunchKernelGGL(kern, dim3(hgrid), dim3(256), (uint32_t)wshm, s, nullptr, nullptr, 0u, h);
-    };
-    switch (a.scan_groups + (dbg ? 8 : 0)) {
-      case 1: half(k_nn_half<1, false>); break;
-      case 2: half(k_nn_half<2, false>); break;
-      case 4: half(k_nn_half<4, false>); break;
-      case 9: half(k_nn_half<1, true>); break;
-      case 10: half(k_nn_half<2, true>); break;
-      case 12: half(k_nn_half<4, true>); break;
-      default: return hipErrorInvalidValue;
-    }
-  }
-  // the wide pass over the overflowed waves and halves (queries already moved: no transform)
-  if (a.fb_list4) {
-    NNLaunch w = a;
-    w.apply = 0;
-    w.wc_box = nullptr;
-    w.wc_ents = nullptr;
-    const int64_t wb = (a.n + 255) / 256;
-    const unsigned ggrid = (unsigned)(wb < 2048 ? wb : 2048);
-    const size_t gshm = (size_t)(256 / 64) * kWideLds;
-    auto wide = [&](auto kern) {
-      hipExtLaunchKernelGGL(kern, dim3(ggrid), dim3(256), (uint32_t)gshm, s, nullptr, nullptr, 0u, w);
-    };
-    switch (a.scan_groups + (dbg ? 8 : 0)) {
-      case 1: wide(k_nn_wide<1, false>); break;
-      case 2: wide(k_nn_wide<2, false>); break;
-      case 4: wide(k_nn_wide<4, false>); break;
-      case 9: wide(k_nn_wide<1, true>); break;
-      case 10: wide(k_nn_wide<2, true>); break;
-      case 12: wide(k_nn_wide<4, true>); break;
-      default: return hipErrorInvalidValue;
-    }
-  }
-  // the follow-up lists are short (the ball list ~0.1 % of the queries, the exact list usually
-  // empty): one launch of 64-thread blocks, grid-stride over them; LDS for the group stacks and
-  // lists or, before them, one DFS stack of `levels` entries per thread
-  const int64_t bq = (a.n + kBallGroups - 1) / kBallGroups;
-  size_t bshm = (size_t)levels * 64 * sizeof(unsigned long long);
-  if (bshm < (size_t)kBallLdsBytes) bshm = kBallLdsBytes;
-  NNLaunch b = a;
-  if (bshm < (size_t)kBBStack * sizeof(int32_t)) bshm = (size_t)kBBStack * sizeof(int32_t);  // wave_bb's stack
-  b.ball_queue_off = (int32_t)bshm;  // the follow-up queue (64 entries + guesses) after the stacks and lists
-  // after the wide pass the list holds what it left: far queries (lanes that joined no box, and
-  // lanes the wide pass could not certify, with its bounds): whole queries per wave
-  if (a.fb_list4 && b.ball_mode == 0) b.ball_mode = 2;
-  bshm += 64 * (sizeof(int32_t) + sizeof(double));
-  hipExtLaunchKernelGGL(k_nn_ball, dim3((unsigned)(bq < 8192 ? bq : 8192)), dim3(64), (uint32_t)bshm, s, nullptr,
-                        nullptr, 0u, b);
-  return hipGetLastError();
+  return launch_nn_follow(a, s);
 }
+
 
 }  // namespace icp
 

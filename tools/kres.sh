@@ -1,10 +1,18 @@
 #!/bin/bash
-# Per-kernel resource usage (VGPRs, scratch, spills, occupancy) of one HIP source, compiled as the
-# Makefile does: bash tools/kres.sh [SOURCE] [FILTER-REGEX]  (run from the repo root, build container)
-SRC=${1:-iterativeclosestpoint_amd/csrc/nn_kernels.hip}
-FILT=${2:-.}
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclude --offload-arch=gfx950 ${EXTRA:-} -c "$SRC" -o /tmp/kres.o \
-  -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c '
+# Per-kernel resource usage (VGPRs, scratch, spills, occupancy) of HIP sources, compiled as the
+# Makefile does: bash tools/kres.sh [SOURCE...] [-f FILTER-REGEX]  (run from the repo root, build
+# container). Default: both search units.
+SRCS=()
+FILT=.
+while [ $# -gt 0 ]; do
+  if [ "$1" = "-f" ]; then FILT=$2; shift 2; else SRCS+=("$1"); shift; fi
+done
+[ ${#SRCS[@]} -gt 0 ] || SRCS=(iterativeclosestpoint_amd/csrc/nn_kernels.hip iterativeclosestpoint_amd/csrc/nn_ball.hip)
+OBJ=$(mktemp /tmp/kres.XXXXXX.o)
+for SRC in "${SRCS[@]}"; do
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclude --offload-arch=gfx950 ${EXTRA:-} -c "$SRC" -o "$OBJ" \
+    -Rpass-analysis=kernel-resource-usage 2>&1
+done | python3 -c '
 import re, sys, subprocess
 rows, cur = [], None
 for line in sys.stdin:
@@ -23,3 +31,4 @@ for r, n in zip(rows, names):
     g = lambda k: r.get(k, "?")
     print("%-60s vgpr %4s scratch %4s vspill %3s sspill %4s occ %s" % (n[:60], g("VGPRs"), g("ScratchSize [bytes/lane]"), g("VGPRs Spill"), g("SGPRs Spill"), g("Occupancy [waves/SIMD]")))
 ' "$FILT"
+rm -f "$OBJ"
