@@ -222,6 +222,10 @@ typedef struct icp_hip_config {
 #define ICP_DBG_BB_OVERFLOW 37   /* cooperative searches whose frontier still outgrew the stack  */
 #define ICP_DBG_LANE_EXACT 38    /* queries the ball search finished by the reference-order DFS
                                     after the cooperative search (a tie or an overflow)          */
+#define ICP_DBG_PREWALK_RETRIES 22  /* product build: prewalks whose B+ overflowed and walked again with
+                                     * a quarter of the margin and the lead                           */
+#define ICP_DBG_PREWALK_KEPT_OLD 23 /* product build: prewalks that still overflowed (the old record stays) */
+#define ICP_DBG_PREWALK_STORES 39 /* candidate records stored by the prewalk after the last iterate */
 #define ICP_DBG_SLOTS 40
 
 typedef struct icp_hip_ctx icp_hip_ctx;
@@ -417,6 +421,19 @@ int icp_hip_last_cull_path(icp_hip_ctx* ctx, int32_t* fused);
 /* The wave search's diagnostic counters of the last iterate (ICP_DBG_* slots); zeros unless the
  * context was created with debug_counters = 1. */
 int icp_hip_debug_counters(icp_hip_ctx* ctx, uint64_t out[ICP_DBG_SLOTS]);
+
+/* Tuning: the prewalk of the candidate cache. After the search of a host-driven iterate that
+ * applied a transform, the waves whose search box would leave their cached candidate record within
+ * `look_ahead` more iterates of the same motion get a fresh record on a second stream, while the
+ * iterate's statistics kernels run, instead of walking the octree inside the next search. Results
+ * do not depend on it (a record of any box is exact). look_ahead in [0, 64]; 0 switches it off.
+ * Without a call the library's built-in default (-DICP_PREWALK_LOOK, 0 = off) applies, and only
+ * to sources of at least 2^20 points; a call applies to sources of any size. Iterates of the
+ * device-resident loop (config.device_loop) never prewalk. A multi-device context passes the
+ * setting to every member. The first call with look_ahead > 0 creates the context's second stream
+ * and the request buffers (32 B per wave of the source); a context that never prewalks has neither.
+ * ICP_HIP_ENOMEM when they cannot be made (the context goes on without the prewalk). */
+int icp_hip_set_prewalk(icp_hip_ctx* ctx, double look_ahead);
 
 int icp_hip_synchronize(icp_hip_ctx* ctx);
 

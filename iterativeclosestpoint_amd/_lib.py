@@ -31,11 +31,12 @@ DBG_NAMES = {0: "waves", 1: "overflow_waves", 2: "not_joined", 3: "not_covered",
              8: "fp64_scan_waves", 9: "staged_points", 10: "scan_pairs", 11: "scan_rounds",
              12: "cache_hits", 13: "cache_stores",
              5: "walk_batches", 6: "no_guess", 7: "candidates", 14: "ball_overflow", 15: "ball_points",
-             21: "start_nodes", 20: "winner_prev_waves", 22: "winner_prev", 23: "winner_lanes",
+             21: "start_nodes", 20: "winner_prev_waves", 22: "prewalk_retries", 23: "prewalk_kept_old",
              18: "prev_cert_waves", 19: "prev_cert_lanes", 16: "halves", 17: "reused_entries",
              24: "walk_moved", 25: "walk_loose", 26: "group_points", 27: "bb_queries", 28: "bb_steps",
              29: "lane_handed", 30: "fz_recompute", 31: "fz_band", 32: "wide_waves", 33: "wide_segments",
-             34: "wide_stack", 35: "wide_undecided", 36: "wide_points", 37: "bb_overflow", 38: "lane_exact"}
+             34: "wide_stack", 35: "wide_undecided", 36: "wide_points", 37: "bb_overflow", 38: "lane_exact",
+             39: "prewalk_stores"}
 
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
@@ -181,6 +182,7 @@ SIGNATURES = {
     "icp_hip_target_build_info": (C.c_int, [_P, _I32, _D]),
     "icp_hip_copy_target": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "icp_hip_target_separation": (C.c_int, [_P, _P]),
+    "icp_hip_set_prewalk": (C.c_int, [_P, C.c_double]),
     "icp_hip_synchronize": (C.c_int, [_P]),
     "icp_hip_comm_abort": (C.c_int, [_P]),
     "icp_hip_debug_inject_failure": (C.c_int, [_P, C.c_int, C.c_int]),
@@ -487,6 +489,10 @@ class Context:
         n, r, d, t = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         _check(lib().icp_hip_comm_info(self._h, member, C.byref(n), C.byref(r), C.byref(d), C.byref(t)))
         return {"count": n.value, "rank": r.value, "device": d.value, "transport": t.value}
+
+    def set_prewalk(self, look_ahead: float):
+        """The candidate cache's prewalk (icp_hip_set_prewalk): look-ahead in iterates, 0 = off."""
+        _check(lib().icp_hip_set_prewalk(self._h, float(look_ahead)))
 
     def synchronize(self):
         _check(lib().icp_hip_synchronize(self._h))

@@ -72,7 +72,78 @@ void dfree(T*& p) {
 
 void icp_ctx_set_error(const char* msg) { g_err = msg; }
 
+// The prewalk's side stream drained: nothing of the last iterate's prewalk is running (before the
+// record buffers are freed, regenerated or read, and before the debug counters are read).
+static void drain_prewalk(icp_hip_ctx* c) {
+  if (c->pw_stream && c->pw_pending) (void)hipStreamSynchronize(c->pw_stream);
+  c->pw_pending = false;
+}
+
+// The prewalk's look-ahead without a setter call (0: off).
+#ifndef ICP_PREWALK_LOOK
+#define ICP_PREWALK_LOOK 0
+#endif
+// ... which applies from this many waves up: below, an iterate is too short to hide a second
+// stream's launches behind its statistics kernels (100k points: ~70 us per iterate).
+static constexpr int64_t kPrewalkMinWaves = 16384;
+// The side stream at the device's lowest stream priority (1), so that its waves are dispatched
+// behind the statistics kernels of the main stream, or at the default priority (0).
+#ifndef ICP_PREWALK_LOW_PRIO
+#define ICP_PREWALK_LOW_PRIO 1
+#endif
+// The next search after a prewalk waits for it on the device (0: hipStreamWaitEvent in front of
+// the search) or on the host (1: before the search is enqueued).
+#ifndef ICP_PREWALK_JOIN_HOST
+#define ICP_PREWALK_JOIN_HOST 0
+#endif
+
+// What the prewalk needs beyond the candidate cache, made when it is first switched on (the
+// setter, or a build whose default look-ahead is not 0) and for every source set after that: the
+// side stream, its two events and the request counter (once per context), the request records
+// (stamp 0: none) and the list, capped at an eighth of the waves (per source). A context that
+// never prewalks has none of it. false: something could not be made; the context then runs
+// without the prewalk (identical results) and `what` says why.
+static bool ensure_prewalk(icp_hip_ctx* c, const char** what) {
+  if (!c->pw_stream) {
+    int prio_least = 0, prio_greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+    if (hipStreamCreateWithPriority(&c->pw_stream, hipStreamNonBlocking, ICP_PREWALK_LOW_PRIO ? prio_least : 0) !=
+            hipSuccess &&
+        hipStreamCreateWithFlags(&c->pw_stream, hipStreamNonBlocking) != hipSuccess) {
+      (void)hipGetLastError();
+      c->pw_stream = nullptr;
+      *what = "the prewalk's stream could not be created";
+      return false;
+    }
+  }
+  if ((!c->ev_pw_fork && hipEventCreateWithFlags(&c->ev_pw_fork, hipEventDisableTiming) != hipSuccess) ||
+      (!c->ev_pw_done && hipEventCreateWithFlags(&c->ev_pw_done, hipEventDisableTiming) != hipSuccess) ||
+      (!c->pw_count && dalloc(&c->pw_count, 1) != hipSuccess)) {
+    (void)hipGetLastError();
+    *what = "the prewalk's events or counter could not be created";
+    return false;
+  }
+  if (c->wc_box && c->n_src > 0 && (!c->wc_req || !c->pw_list)) {
+    const size_t nw = (size_t)((c->n_src + 63) / 64);
+    dfree(c->wc_req);
+    dfree(c->pw_list);
+    c->pw_cap = (unsigned int)(nw / 8 > 64 ? nw / 8 : 64);
+    if (dalloc(&c->wc_req, 2 * nw) != hipSuccess || dalloc(&c->pw_list, 8 * (size_t)c->pw_cap) != hipSuccess ||
+        hipMemsetAsync(c->wc_req, 0, 2 * nw * sizeof(int4), c->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      dfree(c->wc_req);
+      dfree(c->pw_list);
+      *what = "no memory for the prewalk's request records";
+      return false;
+    }
+  }
+  return true;
+}
+
 static void free_source(icp_hip_ctx* c) {
+  drain_prewalk(c);
+  dfree(c->wc_req);
+  dfree(c->pw_list);
   dfree(c->x);
   dfree(c->y);
   dfree(c->z);
@@ -98,6 +169,7 @@ static hipError_t reset_band(icp_hip_ctx* c) {
 }
 
 static void free_target(icp_hip_ctx* c) {
+  drain_prewalk(c);
   dfree(c->nodes);
   dfree(c->tbox);
   dfree(c->pts);
@@ -169,6 +241,8 @@ static void warm_kernels(int device, const icp_hip_config& conf) {
   icp_hip_ctx* w = nullptr;
   if (icp_synth_pair(&sp, kN, kN, tgt.data(), src.data(), Ttrue) == 0 && icp_hip_create_ex(&w, device, &wc) == 0 &&
       icp_hip_set_target(w, tgt.data(), kN, 10, 20, ICP_RULES_ENGINE) == 0 && icp_hip_set_source(w, src.data(), kN) == 0) {
+    // (the prewalk's kernels too, where the build switches it on: the default skips a source this small)
+    if ((double)(ICP_PREWALK_LOOK) > 0.0) (void)icp_hip_set_prewalk(w, (double)(ICP_PREWALK_LOOK));
     const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     icp_iter_stats st;
     for (int k = 0; k < 3; ++k)
@@ -265,6 +339,7 @@ int icp_hip_create_ex(icp_hip_ctx** out, int device, const icp_hip_config* cfg) 
   }
   for (hipEvent_t* ev : {&c->ev_it0, &c->ev_it1}) (void)hipEventCreate(ev);
   (void)hipEventCreateWithFlags(&c->ev_batch, hipEventDisableSystemFence);
+  c->pw_look = (double)(ICP_PREWALK_LOOK);  // (its stream and buffers: ensure_prewalk, at set_source)
   // The per-iterate timing ring only measures elapsed times: no system-scope fence on record
   // (a default event's release writes back L2, ~5 us of GPU idle per record between kernels).
   for (auto& r : c->ring)
@@ -273,7 +348,8 @@ int icp_hip_create_ex(icp_hip_ctx** out, int device, const icp_hip_config* cfg) 
       hipHostMalloc(reinterpret_cast<void**>(&c->h_it), sizeof(IterDev), hipHostMallocMapped | hipHostMallocCoherent) !=
           hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_it_dev), c->h_it, 0) != hipSuccess ||
-      dalloc(&c->counters, 2) != hipSuccess || dalloc(&c->fb_count, 8) != hipSuccess || dalloc(&c->loopd, 1) != hipSuccess ||
+      dalloc(&c->counters, 2) != hipSuccess || dalloc(&c->fb_count, 8) != hipSuccess ||
+      dalloc(&c->loopd, 1) != hipSuccess ||
       dalloc(&c->tickets, (size_t)ticket_words()) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&c->h_loop), sizeof(LoopDev)) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&c->h_ring), icp_hip_ctx::kLoopRing * sizeof(LoopRec),
@@ -302,9 +378,15 @@ void icp_hip_destroy(icp_hip_ctx* c) {
     return;
   }
   (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->pw_stream) (void)hipStreamSynchronize(c->pw_stream);
+  c->pw_pending = false;
   free_source(c);
   free_target(c);
+  dfree(c->pw_count);
+  if (c->ev_pw_fork) (void)hipEventDestroy(c->ev_pw_fork);
+  if (c->ev_pw_done) (void)hipEventDestroy(c->ev_pw_done);
+  if (c->pw_stream) (void)hipStreamDestroy(c->pw_stream);
   dfree(c->it);
   dfree(c->counters);
   dfree(c->fb_count);
@@ -615,6 +697,12 @@ int icp_hip_set_source(icp_hip_ctx* c, const double* xyz, int64_t n) {
     const size_t nw = (size_t)((n + 63) / 64);
     if (dalloc(&c->wc_box, nw) == hipSuccess && dalloc(&c->wc_ents, nw * icp::kWaveCandCap) == hipSuccess) {
       HIP_TRY(hipMemsetAsync(c->wc_box, 0, nw * sizeof(icp::WaveBox), c->stream));  // generation 0: invalid
+      // a context with the prewalk switched on: its request records for this source (without
+      // them no prewalk runs: identical results)
+      if (c->pw_look > 0.0) {
+        const char* why = nullptr;
+        (void)ensure_prewalk(c, &why);
+      }
     } else {
       (void)hipGetLastError();
       dfree(c->wc_box);
@@ -737,6 +825,13 @@ static int enqueue_iterate(icp_hip_ctx* c, const double* T_apply, bool apply, in
   if (c->comm_aborted)
     return fail(ICP_HIP_ERCCL, "iterate: the communicator was aborted (icp_hip_comm_abort or a peer failure); comm_init again");
   hipStream_t s = c->stream;
+  // the last iterate's prewalk writes the records this search reads (and the debug counters the
+  // memset below clears)
+  if (c->pw_pending) {
+    if (ICP_PREWALK_JOIN_HOST) HIP_TRY(hipEventSynchronize(c->ev_pw_done));
+    else HIP_TRY(hipStreamWaitEvent(s, c->ev_pw_done, 0));
+    c->pw_pending = false;
+  }
   hipEvent_t* ev = c->ring[c->n_iterates % icp_hip_ctx::kTimingRing];
   LoopDev* loop = loop_slot >= 0 ? c->loopd : nullptr;
   NNLaunch a = base_launch(c);
@@ -778,7 +873,29 @@ static int enqueue_iterate(icp_hip_ctx* c, const double* T_apply, bool apply, in
   c->timed[slot] = timed;
   a.ev_start = timed ? ev[0] : nullptr;
   a.ev_fast_done = timed ? ev[1] : nullptr;
+  // The prewalk after a search that reuses and stores records (launch_nn's cache instance: a
+  // transform applied, previous residuals), on host-driven iterates: the device loop's session step
+  // overwrites the transform (LoopDev::core.T) that the prewalk's lead reads while it would run.
+  const int64_t n_waves = (c->n_src + 63) / 64;
+  const bool prewalk = c->pw_look > 0.0 && (c->pw_explicit || n_waves >= kPrewalkMinWaves) && !loop && apply &&
+                       c->have_prev && c->cfg.search == ICP_SEARCH_CERTIFIED && c->wc_box && c->wc_req && c->pw_list &&
+                       c->pw_stream && c->ev_pw_fork && c->ev_pw_done && c->pw_count;
+  if (prewalk) {
+    a.wc_req = c->wc_req;
+    a.wc_stamp = ++c->pw_stamp;
+    a.ev_fork = c->ev_pw_fork;
+    a.pw_look = c->pw_look;
+    a.pw_list = c->pw_list;
+    a.pw_count = c->pw_count;
+    a.pw_cap = c->pw_cap;
+  }
   HIP_TRY(launch_nn(a, s));
+  if (prewalk) {
+    // (pending from here on: a launch that fails half-way may have enqueued its first kernels,
+    // and whatever frees the record buffers drains the side stream first)
+    c->pw_pending = true;
+    HIP_TRY(launch_prewalk(a, c->pw_stream, c->ev_pw_fork, c->ev_pw_done));
+  }
   // residual moments -> mean, std, threshold (no communicator: fused into the last merge level)
   const bool multi = c->comm != nullptr || c->xfn != nullptr;
   if (multi && c->inject_failure == 1) {  // testing hook: fail before joining the exchange
@@ -980,6 +1097,7 @@ int icp_hip_debug_counters(icp_hip_ctx* c, uint64_t out[ICP_DBG_SLOTS]) {
   std::memset(out, 0, ICP_DBG_SLOTS * sizeof(uint64_t));
   if (!c->dbg) return ICP_HIP_OK;
   HIP_TRY(hipSetDevice(c->device));
+  drain_prewalk(c);  // slot ICP_DBG_PREWALK_STORES
   HIP_TRY(hipMemcpyAsync(out, c->dbg, ICP_DBG_SLOTS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ICP_HIP_OK;
@@ -1228,11 +1346,27 @@ int icp_hip_debug_inject_failure(icp_hip_ctx* c, int member, int where) {
   return ICP_HIP_OK;
 }
 
+int icp_hip_set_prewalk(icp_hip_ctx* c, double look_ahead) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null ctx");
+  if (!(look_ahead >= 0.0 && look_ahead <= 64.0)) return fail(ICP_HIP_EINVAL, "set_prewalk: look_ahead out of [0, 64]");
+  if (c->group) return group_set_prewalk(c, look_ahead);
+  if (look_ahead > 0.0) {
+    HIP_TRY(hipSetDevice(c->device));
+    const char* why = "";
+    if (!ensure_prewalk(c, &why)) return fail(ICP_HIP_ENOMEM, std::string("set_prewalk: ") + why);
+  }
+  c->pw_look = look_ahead;
+  c->pw_explicit = true;
+  return ICP_HIP_OK;
+}
+
 int icp_hip_synchronize(icp_hip_ctx* c) {
   if (!c) return fail(ICP_HIP_EINVAL, "null ctx");
   if (c->group) return group_synchronize(c);
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->pw_stream) HIP_TRY(hipStreamSynchronize(c->pw_stream));
+  c->pw_pending = false;
   return ICP_HIP_OK;
 }
 

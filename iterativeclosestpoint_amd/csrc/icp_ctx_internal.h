@@ -114,6 +114,20 @@ struct icp_hip_ctx {
   float4* wc_ents = nullptr;
   uint32_t wc_gen = 1;                   // bumped by set_target / set_source (records of older
                                          // generations are never reused)
+  // The prewalk (launch_prewalk): a second stream refreshes, during an iterate's statistics
+  // kernels, the records the next search would otherwise re-walk. pw_pending: work of the last
+  // iterate may still run on pw_stream (the next search waits for ev_pw_done; everything that
+  // frees, regenerates or reads the record buffers or the debug counters drains the stream first).
+  hipStream_t pw_stream = nullptr;
+  hipEvent_t ev_pw_fork = nullptr, ev_pw_done = nullptr;
+  bool pw_pending = false;
+  double pw_look = 0.0;      // look-ahead in iterates of the current motion (0: off)
+  bool pw_explicit = false;  // set by icp_hip_set_prewalk (the built-in default: large sources only)
+  int4* wc_req = nullptr;    // per-wave request records (NNLaunch::wc_req)
+  double* pw_list = nullptr;
+  unsigned int* pw_count = nullptr;
+  unsigned int pw_cap = 0;
+  uint32_t pw_stamp = 0;
   unsigned int* fb_count = nullptr;
   unsigned int* tickets = nullptr;  // "last block done" counters of the moments and cull launches
                                     // (zero between launches: the last block resets its own)
@@ -200,5 +214,6 @@ int group_debug_counters(icp_hip_ctx* c, uint64_t out[ICP_DBG_SLOTS]);
 int group_exchange_timings(icp_hip_ctx* c, int k, double* ms);
 int group_comm_info(icp_hip_ctx* c, int member, int32_t* count, int32_t* rank, int32_t* device, int32_t* transport);
 int group_synchronize(icp_hip_ctx* c);
+int group_set_prewalk(icp_hip_ctx* c, double look_ahead);
 int group_inject_failure(icp_hip_ctx* c, int member, int where);
 icp_hip_ctx* group_member(icp_hip_ctx* c, int k);

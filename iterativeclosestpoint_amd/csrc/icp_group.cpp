@@ -362,6 +362,14 @@ int group_comm_info(icp_hip_ctx* c, int member, int32_t* count, int32_t* rank, i
   return icp_hip_comm_info(g->members[member], 0, count, rank, device, transport);
 }
 
+int group_set_prewalk(icp_hip_ctx* c, double look_ahead) {
+  for (icp_hip_ctx* m : c->group->members) {
+    const int rc = icp_hip_set_prewalk(m, look_ahead);
+    if (rc != ICP_HIP_OK) return rc;
+  }
+  return ICP_HIP_OK;
+}
+
 int group_cull_path(icp_hip_ctx* c, int32_t* fused) {
   // 1 only when every member's cull took its search's wave records
   int32_t all = 1;

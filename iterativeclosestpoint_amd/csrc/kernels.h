@@ -123,6 +123,16 @@ struct NNLaunch {
   const IterDev* fz;        // the band of this iterate (IterDev::fz_*)
   int32_t ball_queue_off;   // k_nn_ball: byte offset of its follow-up queue in LDS
   int32_t ball_mode;        // icp_hip_config.ball_mode (k_nn_ball's direct mode)
+  // The prewalk (launch_prewalk): a wave that reuses its record leaves its box B here, as the
+  // fp32 keys of its reduction in the record's frame (lo x, y, z, hi x, y, z, the iterate's stamp,
+  // 0: two int4 per wave); null: no prewalk after this search.
+  int4* wc_req;
+  uint32_t wc_stamp;        // request records of this iterate carry this stamp
+  hipEvent_t ev_fork;       // optional: recorded once the wave search and its second passes are enqueued
+  double pw_look;           // a wave asks when B leaves B+ within this many iterates of this motion
+  double* pw_list;          // the requests k_prewalk_filter kept: (B lo, hi in fp64, wave id, 0)
+  unsigned int* pw_count;   // their number (may exceed pw_cap: entries past it were dropped)
+  unsigned int pw_cap;      // capacity of pw_list
 };
 
 // Threads per block of the per-thread search kernels for a given stack depth.
@@ -130,6 +140,13 @@ int nn_block_threads(int levels);
 // The correspondence search of one iterate (nn_kernels.hip): the reference-order kernel, or the
 // wave search, its second passes and the follow-up search.
 hipError_t launch_nn(const NNLaunch& a, hipStream_t s);
+// The prewalk of the candidate cache (nn_kernels.hip), enqueued on a side stream `ps` after `fork`
+// (the search of this iterate is done) and followed by `done`: the waves that reused their record
+// but whose box is about to leave it (within a.pw_look iterates of this iterate's motion, on the
+// side they move to) get a fresh record around their current box, as a walking wave would store
+// it, before the next iterate's search is launched (which waits for `done`). a: the search's own
+// launch record (host-driven iterates: a.loop is null).
+hipError_t launch_prewalk(const NNLaunch& a, hipStream_t ps, hipEvent_t fork, hipEvent_t done);
 // launch_nn's parts in nn_ball.hip: the reference-order kernel (k_nn_ref), and the follow-up search
 // of the lists the wave search left (k_nn_ball; owns its LDS sizing and the ball_mode rule).
 hipError_t launch_nn_ref(const NNLaunch& a, hipStream_t s);

@@ -234,18 +234,31 @@ static_assert(kStatLds <= kWaveLds, "the record's reduction fits the wave's LDS 
 // wave that joins either reuses its record or walks and stores one): a walking wave stores its
 // entries before the scan and then streams them back as a reusing wave does, so the instance
 // carries one scan path (ICP_WALK_STREAM); 2 (NC) a first iterate without a transform (no record
-// is reused or stored: the instance carries no cache code); 0 either.
-template <bool APPLY, int NG, bool CERT, bool HALF, bool DBG, int CM = 0, bool WIDE = false>
-__device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, const int lane, unsigned char* wl) {
-  // previous residuals: known to the WC (yes) and NC (no) instances
-  const bool have_prev = CM == 1 ? true : CM == 2 ? false : a.have_prev != 0;
-  constexpr bool kDbg = DBG && kDbgCounts;
+// is reused or stored: the instance carries no cache code); 0 either; 3 (PRE) the prewalk
+// (k_wave_prewalk): no queries and no scan, the wave's box B is given (pre: lo x, y, z, hi x, y,
+// z; i = the wave's first query), and the wave forms B+, walks, filters and stores the record as
+// a walking wave of the WC instance does, then returns (an overflow after the quarter-margin
+// retry leaves the old record); 4 (WC + requests) the WC instance of an iterate followed by a
+// prewalk: a reusing wave also leaves its box in NNLaunch::wc_req (an instance of its own, so
+// that the WC instance's instruction stream is the same with and without the prewalk in the build).
+enum : int { kCmAny = 0, kCmWC = 1, kCmNC = 2, kCmPre = 3, kCmWCReq = 4 };
+constexpr bool cm_cache(int cm) { return cm == kCmWC || cm == kCmWCReq; }  // the WC instances
+template <bool APPLY, int NG, bool CERT, bool HALF, bool DBG, int CM = kCmAny, bool WIDE = false>
+__device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, const int lane, unsigned char* wl,
+                                            const double* pre = nullptr) {
+  // previous residuals: known to the WC, PRE (yes) and NC (no) instances
+  constexpr bool kCache = cm_cache(CM);    // WC, with or without the prewalk's request store
+  constexpr bool kPre = CM == kCmPre;      // the prewalk
+  constexpr bool kReq = CM == kCmWCReq;    // a reusing wave leaves its box for the prewalk
+  const bool have_prev = (kCache || kPre) ? true : CM == kCmNC ? false : a.have_prev != 0;
+  constexpr bool kDbg = DBG && kDbgCounts && !kPre;  // (the prewalk counts its own slots only)
   // a second pass (the half pass, the wide pass): queries already moved, no cache, no wave record
   constexpr bool kSecond = HALF || WIDE;
   static_assert(NG == 1 || NG == 2 || NG == 4, "scan groups: 1, 2 or 4");
   static_assert(!(kSecond && (APPLY || CERT)), "the second passes search moved queries");
   static_assert(!(HALF && WIDE), "one second pass per instance");
-  const bool active = i < a.n;
+  static_assert(!kPre || (APPLY && !CERT && !kSecond), "the prewalk: the lead's transform, no queries");
+  const bool active = !kPre && i < a.n;
   int32_t* queue = reinterpret_cast<int32_t*>(wl);
   double4* stage = reinterpret_cast<double4*>(wl);  // after the walk only
   int32_t* plist = queue + kWaveQueue;               // candidate points
@@ -255,7 +268,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
   // reusing wave has its first chunk before the box is known; unused otherwise).
   const int32_t i0 = __builtin_amdgcn_readfirstlane(i);
   const uint32_t wid = (uint32_t)i0 >> 6;
-  const bool use_wc = !kSecond && CM != 2 && a.wc_box != nullptr && i0 < a.n;
+  const bool use_wc = !kSecond && CM != kCmNC && a.wc_box != nullptr && i0 < a.n;
   // the previous match, whose fl(d2) is u (read unconditionally: an unused load costs no wait,
   // while a conditional one is waited for inside its branch)
   const int32_t prev_pos = qat(a.pos_out, active ? i : 0);
@@ -792,7 +805,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
 
   WaveBox* wb = nullptr;
   float4* wents = nullptr;
-  if (jm != 0) {
+  if (kPre || jm != 0) {
     if (use_wc) {
       wb = a.wc_box + wid;
       wents = a.wc_ents + (size_t)wid * kWaveCandCap;
@@ -819,14 +832,32 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
         atomicAdd(&a.dbg[ICP_DBG_CACHE_HITS], 1ull);
         atomicAdd(&a.dbg[ICP_DBG_REUSED_ENTRIES], (unsigned long long)nleaf);  // entries a reusing wave streams
       }
+      if constexpr (kReq) {
+        // the prewalk's request record: B as the reduction's keys (k_prewalk_filter decides)
+        if (lane == 0) {
+          int4* rq = a.wc_req + 2 * (size_t)wid;
+          rq[0] = make_int4(wkl[0], wkl[1], wkl[2], wkh[0]);
+          rq[1] = make_int4(wkh[1], wkh[2], (int)a.wc_stamp, 0);
+        }
+      }
     } else {
-      // B in fp64: o + the wave's bounds, rounded outwards
-      blx = uniform_d(box_lo(ox_, funkey(wkl[0])));
-      bly = uniform_d(box_lo(oy_, funkey(wkl[1])));
-      blz = uniform_d(box_lo(oz_, funkey(wkl[2])));
-      bhx = uniform_d(box_hi(ox_, funkey(wkh[0])));
-      bhy = uniform_d(box_hi(oy_, funkey(wkh[1])));
-      bhz = uniform_d(box_hi(oz_, funkey(wkh[2])));
+      if constexpr (kPre) {
+        // the prewalk: B as k_prewalk_filter rebuilt it from the wave's request
+        blx = pre[0];
+        bly = pre[1];
+        blz = pre[2];
+        bhx = pre[3];
+        bhy = pre[4];
+        bhz = pre[5];
+      } else {
+        // B in fp64: o + the wave's bounds, rounded outwards
+        blx = uniform_d(box_lo(ox_, funkey(wkl[0])));
+        bly = uniform_d(box_lo(oy_, funkey(wkl[1])));
+        blz = uniform_d(box_lo(oz_, funkey(wkl[2])));
+        bhx = uniform_d(box_hi(ox_, funkey(wkh[0])));
+        bhy = uniform_d(box_hi(oy_, funkey(wkh[1])));
+        bhz = uniform_d(box_hi(oz_, funkey(wkh[2])));
+      }
       // B+ (B itself without the cache); an overflowing B+ makes an overflowing wave (its lanes
       // take the ball search; ~0.06 % of the waves at 10M with the default margin). Wave-uniform
       // doubles are kept in scalar registers.
@@ -867,6 +898,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       // (the wide pass walks B in segments during its scan, phase 4)
       if (!WIDE) walk(wlx, wly, wlz, whx, why, whz);
       if (overflow && keep) {
+        if (kPre && DBG && kDbgCounts && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_PREWALK_RETRIES], 1ull);
         // B+ holds too many points: walk again with a quarter of the margin and the lead, and
         // store that list (an overflowing wave that stored nothing would overflow again at every
         // iterate)
@@ -896,7 +928,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       // |offset| <= ext for every point inside B and every joined query (B lies in the frame box)
       ext = dmax_(dmax_(dmax_(bhx - ocx, ocx - blx), dmax_(bhy - ocy, ocy - bly)), dmax_(bhz - ocz, ocz - blz)) *
             (1.0 + 0x1p-40);
-      if (!overflow && (WIDE || nleaf > 0)) {
+      if (!kPre && !overflow && (WIDE || nleaf > 0)) {
         // the group boxes and the queries' offsets again, in the frame
         reduce((float)(qx - ocx), (float)(qy - ocy), (float)(qz - ocz));
         group_bounds((float)(ext * 0x1p-20));
@@ -922,9 +954,9 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
   // are searched again as two 32-query halves (k_nn_half), each with the smaller box of its own
   // balls; an overflowing half hands its queries to the ball search.
   bool deferred = false;
-  if (overflow) {
+  if (!kPre && overflow) {
     if (!kSecond && lane == 0) atomicAdd(a.fb_count + 6, 1u);  // the iteration record's n_wide
-    if (!HALF && CM != 1 && a.fb_list3 != nullptr) {  // the half pass: first iterates only
+    if (!HALF && !kCache && a.fb_list3 != nullptr) {  // the half pass: first iterates only
       // entries (half id, mask of its deferred lanes): the half pass searches exactly these
       const unsigned long long dm = wballot(join);
       deferred = join;
@@ -975,7 +1007,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
   // streamed: the candidates are cache entries (a reusing wave's, or in the WC instance the ones a
   // walking wave stores here: the points of its list inside B+, in list order, before the scan)
   bool streamed = reuse;
-  if constexpr (CM == 1) {
+  if constexpr (kCache || kPre) {
     if (wstore) {
       int wcount = 0;
       double4 nxtp = make_double4(0.0, 0.0, 0.0, 0.0);
@@ -995,6 +1027,10 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
         wcount += __popcll(pm);
       }
       store_header(wcount);
+      if constexpr (kPre) {
+        if (DBG && kDbgCounts && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_PREWALK_STORES], 1ull);
+        return;
+      }
       wstore = false;
       nleaf = wcount;
       // the wave's own stores, read back by other lanes of the wave (same CU: no L1 invalidate)
@@ -1002,6 +1038,10 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
       ent0 = lane < wcount ? wents[lane] : make_float4(0.f, 0.f, 0.f, 0.f);
       streamed = true;
+    }
+    if constexpr (kPre) {  // overflowed twice: the old record stays
+      if (DBG && kDbgCounts && a.dbg && lane == 0) atomicAdd(&a.dbg[ICP_DBG_PREWALK_KEPT_OLD], 1ull);
+      return;
     }
   }
   const int npts = nleaf;
@@ -1155,7 +1195,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
         }
       };
       wave_lds_fence();
-      if (CM == 1 || streamed) {
+      if (kCache || streamed) {
         // Accumulate: each chunk's points are staged behind the previous chunks' (per group),
         // and a scan round runs only when a group's segment would overflow, and at the end. The
         // lockstep scan then pays max over groups of the wave's whole count once, not of every
@@ -1376,7 +1416,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
     double4 nxtp = make_double4(0.0, 0.0, 0.0, 0.0);
     bool nin = false;
     // candidate k: from the walk's list, or the id word of a reused cache entry
-    auto cand_id = [&](int k) { return (CM == 1 || streamed) ? reinterpret_cast<const int32_t*>(wents + k)[3] : plist[k]; };
+    auto cand_id = [&](int k) { return (kCache || streamed) ? reinterpret_cast<const int32_t*>(wents + k)[3] : plist[k]; };
     if (lane < npts) {
       const int32_t g = cand_id(lane);
       const TgtPt* p = a.pts + g;
@@ -1528,8 +1568,17 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
 #ifndef ICP_FIRST_NC
 #define ICP_FIRST_NC 1
 #endif
+// Blocks of the prewalk launch at most (grid-stride over the requests).
+#ifndef ICP_PREWALK_BLOCKS
+#define ICP_PREWALK_BLOCKS 2048
+#endif
+// One wave per workgroup for k_nn_wave (launch_nn); the kernel itself is the same either way.
+#ifndef ICP_WAVE_WG1
+#define ICP_WAVE_WG1 1
+#endif
+constexpr int64_t kWaveWG1MinWaves = 8192;  // ... from this many waves up (launch_nn)
 template <bool APPLY, int NG, bool CERT, bool DBG, int CM>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM == 1 ? ICP_WAVE_WPE_WC : CM == 2 ? ICP_WAVE_WPE_NC : ICP_WAVE_WPE, CM == 1 ? ICP_WAVE_WPE_WC : CM == 2 ? ICP_WAVE_WPE_NC : ICP_WAVE_WPE))) k_nn_wave(NNLaunch a) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(cm_cache(CM) ? ICP_WAVE_WPE_WC : CM == kCmNC ? ICP_WAVE_WPE_NC : ICP_WAVE_WPE, cm_cache(CM) ? ICP_WAVE_WPE_WC : CM == kCmNC ? ICP_WAVE_WPE_NC : ICP_WAVE_WPE))) k_nn_wave(NNLaunch a) {
   if (a.loop && a.loop->core.done) return;  // the device loop's session finished
   extern __shared__ __attribute__((aligned(16))) unsigned long long lds_raw[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1586,6 +1635,82 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ICP_WI
   }
 }
 
+// The prewalk's filter: one thread per wave of the search. A wave that reused its record in this
+// iterate left its box B as fp32 keys in the record's frame (wc_req, stamped with the iterate). B
+// is rebuilt in fp64 from the record's centre, rounded outwards as a walking wave does; the wave
+// asks for a fresh record when B, moved pw_look times this iterate's displacement of its centre
+// (the quantity the stored lead uses, with its cap), leaves the stored B+ on the side it moves to.
+// Requests go to pw_list (one atomic per wave of this kernel); past pw_cap they are dropped: such
+// a wave walks inside the search when it has to, as without the prewalk.
+__global__ void __launch_bounds__(256) k_prewalk_filter(NNLaunch a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = (a.n + 63) >> 6;
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool ask = false;
+  double b[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (w < nw) {
+    const int4 r0 = a.wc_req[2 * w], r1 = a.wc_req[2 * w + 1];
+    const WaveBox* hb = a.wc_box + w;
+    if ((uint32_t)r1.z == a.wc_stamp && hb->gen == a.wc_gen) {
+      const int kl[3] = {r0.x, r0.y, r0.z}, kh[3] = {r0.w, r1.x, r1.y};
+      double T[12];
+      load_T(a, T);
+      double lo[3], hi[3], c[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        lo[k] = hb->lo[k];
+        hi[k] = hb->hi[k];
+        const double o = (lo[k] + hi[k]) * 0.5;  // the frame of the keys: B+'s centre
+        b[k] = box_lo(o, funkey(kl[k]));
+        b[3 + k] = box_hi(o, funkey(kh[k]));
+        c[k] = (b[k] + b[3 + k]) * 0.5;
+      }
+      const double cap = 2.0 * dmax_(dmax_(b[3] - b[0], b[4] - b[1]), b[5] - b[2]);
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const double e = (((T[4 * k] * c[0] + T[4 * k + 1] * c[1]) + T[4 * k + 2] * c[2]) + T[4 * k + 3]) - c[k];
+        const double d = (e == e && __builtin_fabs(e) <= cap) ? a.pw_look * e : 0.0;
+        ask = ask || (d > 0.0 && b[3 + k] + d > hi[k]) || (d < 0.0 && b[k] + d < lo[k]);
+      }
+    }
+  }
+  const unsigned long long am = wballot(ask);
+  if (am == 0) return;
+  unsigned base = 0;
+  if (lane == 0) base = atomicAdd(a.pw_count, (unsigned)__popcll(am));
+  base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+  const unsigned at = base + (unsigned)mask_rank(am);
+  if (ask && at < a.pw_cap) {
+    double* e = a.pw_list + 8 * (size_t)at;
+#pragma unroll
+    for (int k = 0; k < 6; k++) e[k] = b[k];
+    e[6] = __longlong_as_double((long long)w);
+    e[7] = 0.0;
+  }
+}
+
+// The prewalk: every wave takes requests from pw_list (grid-stride; the list is complete when this
+// kernel starts) and stores the record of the request's wave (wave_search's PRE instance).
+template <bool DBG>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_wave_prewalk(NNLaunch a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long lds_raw[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  unsigned char* wl = reinterpret_cast<unsigned char*>(lds_raw) + wv * kWaveLds;
+  const unsigned listed = *a.pw_count;
+  const unsigned cnt = listed < a.pw_cap ? listed : a.pw_cap;
+  const unsigned waves = gridDim.x * (blockDim.x >> 6);
+  for (unsigned j = blockIdx.x * (blockDim.x >> 6) + wv; j < cnt; j += waves) {
+    const double* e = a.pw_list + 8 * (size_t)j;
+    double pre[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) pre[k] = uniform_d(e[k]);
+    const int64_t w = __builtin_amdgcn_readfirstlane((int)__double_as_longlong(e[6]));
+    if (w < 0 || w >= ((a.n + 63) >> 6)) continue;  // (never: the filter lists waves of this source)
+    wave_lds_fence();  // the previous request's LDS reads are done
+    wave_search<true, 1, false, false, DBG, kCmPre>(a, (int32_t)(w * 64) + lane, lane, wl, pre);
+  }
+}
+
 // The instances' compile-time choices from the launch's run-time values: f(std::bool_constant),
 // f(std::integral_constant<int, NG>) for the scan groups (1, 2 or 4; anything else launches nothing).
 template <class F>
@@ -1609,8 +1734,17 @@ hipError_t launch_nn(const NNLaunch& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   if (a.search == ICP_SEARCH_REFERENCE || a.count) return launch_nn_ref(a, s);
   // wave search -> ball search -> per-lane search / exact DFS
-  const unsigned wgrid = (unsigned)((a.n + 255) / 256);
-  const size_t wshm = (size_t)(256 / 64) * kWaveLds;
+  // The wave search's workgroups: one wave each (ICP_WAVE_WG1) once the launch has more waves than
+  // are resident at a time (256 CUs x 4 SIMDs x 7 waves). The waves of a block never cooperate,
+  // and LDS is released per workgroup: a block with one long walker holds four waves' LDS while
+  // blocks wait for a slot. A smaller launch is resident at once and starts sooner in blocks of
+  // four waves (100k points: 1.7 % slower in one-wave workgroups). The XCD runs are scaled so that
+  // every XCD takes the same runs of waves; the kernel is the same either way.
+  const unsigned kWG = (ICP_WAVE_WG1 && (a.n + 63) / 64 >= kWaveWG1MinWaves) ? 64u : 256u;
+  const unsigned wgrid = (unsigned)((a.n + kWG - 1) / kWG);
+  const size_t wshm = (size_t)(256 / 64) * kWaveLds, wshm1 = (size_t)(kWG / 64) * kWaveLds;
+  NNLaunch aw = a;
+  aw.xcd_blocks = a.xcd_blocks * (int)(256u / kWG);
   // The second passes search queries that are already moved: no transform, no cache. About one
   // resident block per slot.
   NNLaunch h = a;
@@ -1637,12 +1771,13 @@ hipError_t launch_nn(const NNLaunch& a, hipStream_t s) {
       // by the next kernel's dispatch instead measured no better), so the context times only every
       // config.timing_stride-th iterate (null events: plain launches).
       auto wave = [&](auto kern) {
-        hipExtLaunchKernelGGL(kern, dim3(wgrid), dim3(256), (uint32_t)wshm, s, a.ev_start, a.ev_fast_done, 0u, a);
+        hipExtLaunchKernelGGL(kern, dim3(wgrid), dim3(kWG), (uint32_t)wshm1, s, a.ev_start, a.ev_fast_done, 0u, aw);
       };
       with_flag(cert, [&](auto cert_c) {
         constexpr bool C = decltype(cert_c)::value;
-        if (wc) wave(k_nn_wave<true, G, C, D, 1>);
-        else if (nc) wave(k_nn_wave<false, G, C, D, 2>);
+        if (wc && a.wc_req) wave(k_nn_wave<true, G, C, D, kCmWCReq>);
+        else if (wc) wave(k_nn_wave<true, G, C, D, kCmWC>);
+        else if (nc) wave(k_nn_wave<false, G, C, D, kCmNC>);
         else if (a.apply) wave(k_nn_wave<true, G, C, D, 0>);
         else wave(k_nn_wave<false, G, C, D, 0>);
       });
@@ -1655,7 +1790,31 @@ hipError_t launch_nn(const NNLaunch& a, hipStream_t s) {
     });
   });
   if (pe != hipSuccess) return pe;
+  // the prewalk's fork: the wave search and its second passes are enqueued
+  if (a.ev_fork) {
+    const hipError_t fe = hipEventRecord(a.ev_fork, s);
+    if (fe != hipSuccess) return fe;
+  }
   return launch_nn_follow(a, s);
+}
+
+hipError_t launch_prewalk(const NNLaunch& a, hipStream_t ps, hipEvent_t fork, hipEvent_t done) {
+  if (a.n <= 0 || !a.wc_req || !a.wc_box || !a.wc_ents || !a.pw_list || !a.pw_count || a.pw_cap == 0 || a.loop)
+    return hipErrorInvalidValue;
+  hipError_t e = hipStreamWaitEvent(ps, fork, 0);
+  if (e == hipSuccess) e = hipMemsetAsync(a.pw_count, 0, sizeof(unsigned int), ps);
+  if (e != hipSuccess) return e;
+  const int64_t nw = (a.n + 63) / 64;
+  hipLaunchKernelGGL(k_prewalk_filter, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, ps, a);
+  // one wave per possible request, up to about one resident block per slot
+  const int64_t pb = ((int64_t)a.pw_cap + 3) / 4;
+  const unsigned pgrid = (unsigned)(pb < ICP_PREWALK_BLOCKS ? pb : ICP_PREWALK_BLOCKS);
+  const size_t pshm = (size_t)(256 / 64) * kWaveLds;
+  if (a.dbg) hipLaunchKernelGGL(k_wave_prewalk<true>, dim3(pgrid), dim3(256), (uint32_t)pshm, ps, a);
+  else hipLaunchKernelGGL(k_wave_prewalk<false>, dim3(pgrid), dim3(256), (uint32_t)pshm, ps, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return hipEventRecord(done, ps);
 }
 
 
