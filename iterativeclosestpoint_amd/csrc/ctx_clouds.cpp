@@ -1,0 +1,440 @@
+// ctx_clouds.cpp — the clouds resident on the device: the target's octree, this rank's source shard
+// in query order, and the calls that read them back or search the target outside an iterate.
+#include <cfloat>
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+#include "icp_ctx_internal.h"
+#include "octree_build.h"
+#include "octree_gpu.h"
+#include "query_order.h"
+
+using namespace icp;
+
+void free_source(icp_hip_ctx* c) {
+  prewalk_free_source(c);
+  dfree(c->x);
+  dfree(c->y);
+  dfree(c->z);
+  dfree(c->perm);
+  dfree(c->pos);
+  dfree(c->dist);
+  dfree(c->fb_list);
+  dfree(c->fb_u);
+  dfree(c->wc_box);
+  dfree(c->wc_ents);
+  dfree(c->mparts);
+  dfree(c->cparts);
+  dfree(c->wstat);
+  c->n_src = 0;
+}
+
+// No band for the next iterate's search (a new source or target): its cull pass does it all.
+static hipError_t reset_band(icp_hip_ctx* c) {
+  c->last_cull_path = -1;
+  char* base = reinterpret_cast<char*>(c->it);
+  return hipMemsetAsync(base + offsetof(IterDev, fz_lo), 0, offsetof(IterDev, cull_mode) - offsetof(IterDev, fz_lo),
+                        c->stream);
+}
+
+void free_target(icp_hip_ctx* c) {
+  drain_prewalk(c);
+  dfree(c->nodes);
+  dfree(c->tbox);
+  dfree(c->pts);
+  dfree(c->cells);
+  c->cell_lmax = -1;
+  c->n_nodes = 0;
+  c->n_tgt = 0;
+}
+
+NNLaunch base_launch(const icp_hip_ctx* c) {
+  NNLaunch a;
+  std::memset(&a, 0, sizeof(a));
+  a.nodes = c->nodes;
+  a.tbox = c->tbox;
+  a.pts = c->pts;
+  a.counters = c->counters;
+  a.n_nodes = (int32_t)c->n_nodes;
+  a.pos0 = c->pos0;
+  a.levels = c->levels;
+  a.init_best = c->init_best;
+  a.search = c->cfg.search;
+  a.scan32 = c->cfg.scan32;
+  a.cells = c->cells;
+  a.cell_lmax = c->cell_lmax;
+  a.join_factor = c->cfg.join_factor;
+  a.ball_mode = c->cfg.ball_mode;
+  a.xcd_blocks = c->cfg.xcd_blocks;
+  a.scan_groups = c->cfg.scan_groups;
+  a.certify_prev = c->cfg.certify_prev;
+  a.dbg = c->dbg;
+  for (int k = 0; k < 3; k++) {
+    a.root_lo[k] = c->root_box[k];
+    a.root_hi[k] = c->root_box[3 + k];
+  }
+  return a;
+}
+
+// What the context keeps of a built tree besides its arrays (GpuOctree or FlatOctree).
+template <class Tree>
+static void keep_tree_info(icp_hip_ctx* c, const Tree& t, int64_t n_nodes) {
+  c->n_nodes = n_nodes;
+  c->n_leaves = t.n_leaves;
+  c->pos0 = t.pos_of_orig0;
+  c->max_depth = t.max_depth;
+  c->levels = t.max_inner_depth + 1 > 0 ? t.max_inner_depth + 1 : 1;
+}
+
+extern "C" {
+
+int icp_hip_set_target(icp_hip_ctx* c, const double* xyz, int64_t n, int max_points, int max_depth, int rules) {
+  if (!c || (!xyz && n > 0)) return fail(ICP_HIP_EINVAL, "null argument");
+  if (c->group) return n <= 0 ? fail(ICP_HIP_EINVAL, "empty target cloud (icpengine.cpp:31-34 rejects it)")
+                             : group_set_target(c, xyz, n, max_points, max_depth, rules);
+  if (n <= 0) return fail(ICP_HIP_EINVAL, "empty target cloud (icpengine.cpp:31-34 rejects it)");
+  if (max_depth < 0 || max_depth > 60) return fail(ICP_HIP_EINVAL, "max_depth out of range [0, 60]");
+  if (n > (int64_t)0x7fffffff) return fail(ICP_HIP_EINVAL, "target size out of range (int32 indices, as the reference)");
+  HIP_TRY(hipSetDevice(c->device));
+  free_target(c);
+  HIP_TRY(reset_band(c));
+  hipEvent_t e0 = c->ev_it0, e1 = c->ev_it1;
+  HIP_TRY(hipEventRecord(e0, c->stream));
+  const bool on_device = max_depth <= kGpuBuildMaxDepth && c->cfg.octree_builder == ICP_BUILD_AUTO;
+  if (on_device) {
+    // device build straight from the uploaded AoS cloud (octree_gpu.hip)
+    double* d_xyz = nullptr;
+    HIP_TRY(dalloc(&d_xyz, 3 * (size_t)n));
+    hipError_t e = hipMemcpyAsync(d_xyz, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+      dfree(d_xyz);
+      return fail(ICP_HIP_EDEVICE, std::string("set_target upload: ") + hipGetErrorString(e));
+    }
+    GpuOctree t;
+    std::string why;
+    const int rc = gpu_build_octree(d_xyz, n, max_points, max_depth, c->stream, &t, &why);
+    dfree(d_xyz);
+    if (rc != 0) return fail(rc == 1 ? ICP_HIP_EINVAL : rc == -2 ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, why);
+    c->nodes = t.nodes;
+    c->pts = t.pts;
+    keep_tree_info(c, t, t.n_nodes);
+  } else {
+    FlatOctree t;
+    const char* why = nullptr;
+    if (!build_flat_octree(xyz, n, max_points, max_depth, &t, &why)) return fail(ICP_HIP_EINVAL, why ? why : "bad target");
+    HIP_TRY(dalloc(&c->nodes, t.nodes.size()));
+    HIP_TRY(dalloc(&c->pts, t.pts.size()));
+    HIP_TRY(hipMemcpyAsync(c->nodes, t.nodes.data(), t.nodes.size() * sizeof(NodeRec), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->pts, t.pts.data(), t.pts.size() * sizeof(TgtPt), hipMemcpyHostToDevice, c->stream));
+    keep_tree_info(c, t, (int64_t)t.nodes.size());
+  }
+  // separation of every target point (the previous-match certificate, certify_prev)
+  if (c->cfg.certify_prev) HIP_TRY(launch_target_sep(c->nodes, c->pts, n, c->levels, c->stream));
+  // after the separations (which a copy's flag overwrites: its separation is 0 either way)
+  HIP_TRY(launch_mark_copies(c->pts, n, c->stream));
+  HIP_TRY(dalloc(&c->tbox, (size_t)c->n_nodes));
+  HIP_TRY(launch_tight_boxes(c->nodes, c->pts, c->tbox, c->n_nodes, c->max_depth, c->stream));
+  // root box (host copy: the kernels' cell arithmetic starts from it) and the cell tables
+  {
+    NodeRec root;
+    HIP_TRY(hipMemcpyAsync(&root, c->nodes, sizeof(NodeRec), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; k++) {
+      c->root_box[k] = root.lo[k];
+      c->root_box[3 + k] = root.hi[k];
+    }
+  }
+  if (c->cfg.cell_starts && c->n_nodes < ((int64_t)1 << 26)) {
+    const int lmax = cell_table_depth(c->n_leaves, c->levels - 1);
+    // the tables only speed up the searches' start: without memory for them the searches start
+    // from the root (identical results)
+    if (dalloc(&c->cells, (size_t)cell_table_entries(lmax)) == hipSuccess) {
+      HIP_TRY(build_cell_tables(c->nodes, lmax, c->cells, c->stream));
+      c->cell_lmax = lmax;
+    } else {
+      (void)hipGetLastError();
+      c->cells = nullptr;
+    }
+  }
+  HIP_TRY(hipEventRecord(e1, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  c->target_build_ms = ms;
+  c->target_on_device = on_device ? 1 : 0;
+  c->n_tgt = n;
+  c->init_best = (rules == ICP_RULES_CLI) ? 1e20 : DBL_MAX;  // icp_registration.cpp:201 / octree.cpp:180
+  c->have_prev = false;
+  c->wc_gen++;  // cached candidate lists name points of the previous tree
+  c->have_results = false;
+  return ICP_HIP_OK;
+}
+
+int icp_hip_target_build_info(icp_hip_ctx* c, int32_t* on_device, double* build_ms) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null context");
+  if (c->group) return group_target_build_info(c, on_device, build_ms);
+  if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
+  if (on_device) *on_device = c->target_on_device;
+  if (build_ms) *build_ms = c->target_build_ms;
+  return ICP_HIP_OK;
+}
+
+int icp_hip_copy_target(icp_hip_ctx* c, double* box6, int32_t* first, uint32_t* meta, int32_t* depth, double* xyz,
+                        int32_t* orig) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null context");
+  if (c->group) return icp_hip_copy_target(group_member(c, 0), box6, first, meta, depth, xyz, orig);
+  if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<NodeRec> nodes((size_t)c->n_nodes);
+  std::vector<TgtPt> pts((size_t)c->n_tgt);
+  HIP_TRY(hipMemcpyAsync(nodes.data(), c->nodes, nodes.size() * sizeof(NodeRec), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(pts.data(), c->pts, pts.size() * sizeof(TgtPt), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const NodeRec& r = nodes[i];
+    if (box6)
+      for (int k = 0; k < 3; k++) {
+        box6[6 * i + k] = r.lo[k];
+        box6[6 * i + 3 + k] = r.hi[k];
+      }
+    if (first) first[i] = r.first;
+    if (meta) meta[i] = r.meta;
+    if (depth) depth[i] = r.depth;
+  }
+  for (size_t i = 0; i < pts.size(); i++) {
+    if (xyz) {
+      xyz[3 * i] = pts[i].x;
+      xyz[3 * i + 1] = pts[i].y;
+      xyz[3 * i + 2] = pts[i].z;
+    }
+    if (orig) orig[i] = pts[i].orig;
+  }
+  return ICP_HIP_OK;
+}
+
+int icp_hip_target_separation(icp_hip_ctx* c, float* sep_out) {
+  if (!c || !sep_out) return fail(ICP_HIP_EINVAL, "null argument");
+  if (c->group) return icp_hip_target_separation(group_member(c, 0), sep_out);
+  if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<TgtPt> pts((size_t)c->n_tgt);
+  HIP_TRY(hipMemcpyAsync(pts.data(), c->pts, pts.size() * sizeof(TgtPt), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (const TgtPt& p : pts) sep_out[p.orig] = p.sep;
+  return ICP_HIP_OK;
+}
+
+int icp_hip_target_info(icp_hip_ctx* c, int64_t* n_nodes, int64_t* n_leaves, int32_t* max_depth, int32_t* levels) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null ctx");
+  if (c->group) return icp_hip_target_info(group_member(c, 0), n_nodes, n_leaves, max_depth, levels);
+  if (n_nodes) *n_nodes = c->n_nodes;
+  if (n_leaves) *n_leaves = c->n_leaves;
+  if (max_depth) *max_depth = c->max_depth;
+  if (levels) *levels = c->levels;
+  return ICP_HIP_OK;
+}
+
+int icp_hip_set_source(icp_hip_ctx* c, const double* xyz, int64_t n) {
+  if (!c || (!xyz && n > 0) || n < 0) return fail(ICP_HIP_EINVAL, "bad source arguments");
+  if (c->group) return group_set_source(c, xyz, n);
+  // the wave search addresses per-query arrays by 32-bit byte offsets (nn_device.h qat): < 2^29
+  // points per shard (12 GB of coordinates; a larger cloud is sharded over a device group)
+  if (n >= ((int64_t)1 << 29)) return fail(ICP_HIP_EINVAL, "source shard of 2^29 points or more");
+  HIP_TRY(hipSetDevice(c->device));
+  free_source(c);
+  c->n_src = n;
+  c->nb_mom = moments_num_parts(n);
+  c->nb_cull = cull_num_blocks(n);
+  HIP_TRY(dalloc(&c->x, n));
+  HIP_TRY(dalloc(&c->y, n));
+  HIP_TRY(dalloc(&c->z, n));
+  HIP_TRY(dalloc(&c->perm, n));
+  HIP_TRY(dalloc(&c->pos, n));
+  HIP_TRY(dalloc(&c->dist, n));
+  HIP_TRY(dalloc(&c->fb_list, 3 * (size_t)n + 64));  // exact, ball, (half, mask) pairs
+  HIP_TRY(dalloc(&c->fb_u, (size_t)n));
+  if (c->cfg.candidate_cache && n > 0) {
+    // the cache only saves walks: without memory for it every iterate walks (identical results)
+    const size_t nw = (size_t)((n + 63) / 64);
+    if (dalloc(&c->wc_box, nw) == hipSuccess && dalloc(&c->wc_ents, nw * icp::kWaveCandCap) == hipSuccess) {
+      HIP_TRY(hipMemsetAsync(c->wc_box, 0, nw * sizeof(icp::WaveBox), c->stream));  // generation 0: invalid
+      prewalk_new_source(c);
+    } else {
+      (void)hipGetLastError();
+      dfree(c->wc_box);
+      dfree(c->wc_ents);
+    }
+  }
+  c->wc_gen++;
+  HIP_TRY(dalloc(&c->mparts, (size_t)(c->nb_mom + merge_scratch_entries(c->nb_mom))));
+  HIP_TRY(dalloc(&c->cparts, (size_t)(c->nb_cull + merge_scratch_entries(c->nb_cull))));
+  if (n > 0 && c->cfg.fused_cull && dalloc(&c->wstat, (size_t)((n + 63) / 64)) != hipSuccess) {
+    (void)hipGetLastError();  // without the records every cull is a full pass (identical results)
+    dfree(c->wstat);
+  }
+  HIP_TRY(reset_band(c));
+  if (n == 0) return ICP_HIP_OK;
+  // Spatially compact query order (kd buckets of 64 = one wave): on the device from the uploaded
+  // cloud (query_order_gpu.hip), or on the host (config query_order = 1)
+  double* aos = nullptr;
+  hipError_t e = dalloc(&aos, 3 * (size_t)n);
+  if (e == hipSuccess) e = hipMemcpyAsync(aos, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    if (c->cfg.query_order == 0) {
+      e = gpu_kd_query_order(aos, n, 8, c->perm, c->stream);
+    } else {
+      std::vector<int32_t> perm;
+      kd_query_order(xyz, n, 8, &perm);
+      e = hipMemcpyAsync(c->perm, perm.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host order is read by the copy
+    }
+  }
+  if (e == hipSuccess) e = launch_gather_deinterleave(aos, c->perm, c->x, c->y, c->z, n, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(aos);
+  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("set_source: ") + hipGetErrorString(e));
+  c->have_results = false;
+  c->have_prev = false;
+  return ICP_HIP_OK;
+}
+
+int icp_hip_apply(icp_hip_ctx* c, const double* T) {
+  if (!c || !T) return fail(ICP_HIP_EINVAL, "null argument");
+  if (c->group) return group_apply(c, T);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(launch_apply(T, c->x, c->y, c->z, c->n_src, c->stream));
+  c->have_prev = false;  // queries moved without a search: previous residuals are no guess
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ICP_HIP_OK;
+}
+
+int icp_hip_get_source(icp_hip_ctx* c, double* xyz_out) {
+  if (c && c->group) return xyz_out ? group_get_source(c, xyz_out) : fail(ICP_HIP_EINVAL, "null argument");
+  if (!c || (!xyz_out && c->n_src > 0)) return fail(ICP_HIP_EINVAL, "null argument");
+  if (c->n_src == 0) return ICP_HIP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  double* aos = nullptr;
+  HIP_TRY(dalloc(&aos, 3 * (size_t)c->n_src));
+  hipError_t e = launch_scatter_aos(c->perm, c->x, c->y, c->z, aos, c->n_src, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(xyz_out, aos, 3 * sizeof(double) * c->n_src, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(aos);
+  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("get_source: ") + hipGetErrorString(e));
+  return ICP_HIP_OK;
+}
+
+int icp_hip_get_correspondences(icp_hip_ctx* c, int32_t* idx_out, double* dist_out) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null argument");
+  if (c->group) return group_get_correspondences(c, idx_out, dist_out);
+  if (!c->have_results) return fail(ICP_HIP_ENOTREADY, "no iteration has run on this source");
+  if (c->n_src == 0) return ICP_HIP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  int32_t* di = nullptr;
+  double* dd = nullptr;
+  hipError_t e = hipSuccess;
+  if (idx_out) e = dalloc(&di, c->n_src);
+  if (e == hipSuccess && dist_out) e = dalloc(&dd, c->n_src);
+  if (e == hipSuccess) e = launch_scatter_corr(c->perm, c->pos, c->pts, di, c->dist, dd, c->n_src, c->stream);
+  if (e == hipSuccess && idx_out) e = hipMemcpyAsync(idx_out, di, sizeof(int32_t) * c->n_src, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && dist_out) e = hipMemcpyAsync(dist_out, dd, sizeof(double) * c->n_src, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(di);
+  dfree(dd);
+  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("get_correspondences: ") + hipGetErrorString(e));
+  return ICP_HIP_OK;
+}
+
+int icp_hip_nn(icp_hip_ctx* c, const double* q, int64_t n, int32_t* idx_out, double* dist_out) {
+  if (!c || n < 0 || (n > 0 && !q)) return fail(ICP_HIP_EINVAL, "bad arguments");
+  if (c->group) return icp_hip_nn(group_member(c, 0), q, n, idx_out, dist_out);  // the replicated octree
+  if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
+  if (n == 0) return ICP_HIP_OK;
+  // the wave search addresses per-query arrays by 32-bit byte offsets (nn_device.h qat): launches
+  // of fewer than 2^29 queries, so larger sets go in slices (the answers are per query)
+  constexpr int64_t kSlice = (int64_t)1 << 28;
+  if (n > kSlice) {
+    unsigned int lists[3] = {0, 0, 0};
+    for (int64_t off = 0; off < n; off += kSlice) {
+      const int64_t m = n - off < kSlice ? n - off : kSlice;
+      const int rc = icp_hip_nn(c, q + 3 * off, m, idx_out ? idx_out + off : nullptr, dist_out ? dist_out + off : nullptr);
+      if (rc != ICP_HIP_OK) return rc;
+      for (int k = 0; k < 3; k++) lists[k] += c->last_lists[k];
+    }
+    for (int k = 0; k < 3; k++) c->last_lists[k] = lists[k];
+    return ICP_HIP_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  double *aos = nullptr, *x = nullptr, *y = nullptr, *z = nullptr, *d = nullptr, *dd = nullptr;
+  int32_t *pos = nullptr, *di = nullptr;
+  hipError_t e = hipSuccess;
+  if ((e = dalloc(&aos, 3 * (size_t)n)) == hipSuccess && (e = dalloc(&x, n)) == hipSuccess &&
+      (e = dalloc(&y, n)) == hipSuccess && (e = dalloc(&z, n)) == hipSuccess && (e = dalloc(&d, n)) == hipSuccess &&
+      (e = dalloc(&dd, n)) == hipSuccess && (e = dalloc(&pos, n)) == hipSuccess && (e = dalloc(&di, n)) == hipSuccess) {
+    e = hipMemcpyAsync(aos, q, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_deinterleave(aos, x, y, z, n, c->stream);
+    NNLaunch a = base_launch(c);
+    a.x = x;
+    a.y = y;
+    a.z = z;
+    a.pos_out = pos;
+    a.dist_out = d;
+    a.n = n;
+    int32_t* fbl = nullptr;
+    double* fbu = nullptr;
+    if (e == hipSuccess) e = dalloc(&fbl, 3 * (size_t)n + 64);
+    if (e == hipSuccess) e = dalloc(&fbu, (size_t)n);
+    a.fb_list = fbl;
+    a.fb_list2 = fbl + n;
+    a.fb_list3 = c->cfg.overflow_halves ? fbl + 2 * n : nullptr;
+    a.fb_list4 = c->cfg.scan32 && c->cfg.wide_pass != 1 ? wide_list(fbl, n) : nullptr;
+    a.fb_u2 = fbu;
+    a.fb_count = c->fb_count;
+    unsigned int lists4[4] = {0, 0, 0, 0};
+    if (e == hipSuccess) e = hipMemsetAsync(c->fb_count, 0, 8 * sizeof(unsigned int), c->stream);
+    c->lists_zero = false;
+    if (e == hipSuccess) e = launch_nn(a, c->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(lists4, c->fb_count, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    c->last_lists[0] = lists4[0] + lists4[3];  // exact: the wave search's list + the ball's DFS finishes
+    c->last_lists[1] = lists4[1];
+    c->last_lists[2] = lists4[2];
+    dfree(fbl);
+    dfree(fbu);
+    if (e == hipSuccess) e = launch_scatter_corr(nullptr, pos, c->pts, di, d, dd, n, c->stream);
+    if (e == hipSuccess && idx_out) e = hipMemcpyAsync(idx_out, di, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && dist_out) e = hipMemcpyAsync(dist_out, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  dfree(aos); dfree(x); dfree(y); dfree(z); dfree(d); dfree(dd); dfree(pos); dfree(di);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, std::string("nn: ") + hipGetErrorString(e));
+  return ICP_HIP_OK;
+}
+
+int icp_hip_traversal_counts(icp_hip_ctx* c, double* mean_entries, double* mean_points) {
+  if (!c || !mean_entries || !mean_points) return fail(ICP_HIP_EINVAL, "null argument");
+  if (c->group) return group_traversal_counts(c, mean_entries, mean_points);
+  if (!c->nodes || (!c->x && c->n_src > 0)) return fail(ICP_HIP_ENOTREADY, "target/source not set");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemsetAsync(c->counters, 0, 2 * sizeof(unsigned long long), c->stream));
+  NNLaunch a = base_launch(c);
+  a.x = c->x;
+  a.y = c->y;
+  a.z = c->z;
+  a.pos_out = c->pos;  // same queries as the last iterate: identical outputs are rewritten
+  a.dist_out = c->dist;
+  a.n = c->n_src;
+  a.dbg = nullptr;
+  a.count = 1;
+  HIP_TRY(launch_nn(a, c->stream));
+  unsigned long long h[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(h, c->counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const double n = c->n_src > 0 ? (double)c->n_src : 1.0;
+  *mean_entries = (double)h[0] / n;
+  *mean_points = (double)h[1] / n;
+  return ICP_HIP_OK;
+}
+
+}  // extern "C"

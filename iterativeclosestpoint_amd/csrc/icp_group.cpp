@@ -52,11 +52,6 @@ struct DeviceGroup {
 
 namespace {
 
-int fail(int code, const std::string& msg) {
-  icp_ctx_set_error(msg.c_str());
-  return code;
-}
-
 // f(k, member) on every member's driver thread, concurrently; the first failure's code and message
 // (the message is thread-local to the driver that saw it) come back to the caller. A failing member
 // raises the group's abort flag, so peers waiting in an exchange or for a record give up.
