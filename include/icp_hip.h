@@ -25,6 +25,7 @@
 #ifndef ICP_HIP_H
 #define ICP_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -390,6 +391,45 @@ int icp_hip_get_correspondences(icp_hip_ctx* ctx, int32_t* idx_out, double* dist
 /* Parity hook: nearest target index + residual for arbitrary queries (AoS), no reordering,
  * no transform — exactly Octree::findNearest + computeDistance per query. */
 int icp_hip_nn(icp_hip_ctx* ctx, const double* q_xyz, int64_t n, int32_t* idx_out, double* dist_out);
+
+/* --- Device-resident clouds. The *_device calls take buffers that already live in HBM (a decoder,
+ * a previous pipeline stage, another context on the same GPU) in the layout of the host calls:
+ * packed AoS xyz fp64 (int32 indices, fp64 residuals for the outputs). They run the same device
+ * core as the host variants minus the scratch copy and the PCIe transfer, so every result is the
+ * host call's bit for bit.
+ * Contract: the buffer belongs to the context's device (device or managed memory); the caller's
+ * work that produced it has completed before the call; the call reads or writes it on the
+ * context's stream and returns after that stream is synchronised, as the host variants do; inputs
+ * are never written and never retained.
+ * Rejected with ICP_HIP_EINVAL before any kernel runs: a null pointer (outputs documented as
+ * optional excepted), n outside the host variant's range, a coordinate or residual pointer that is
+ * not 8-byte aligned (an index pointer: 4), and a pointer that hipPointerGetAttributes does not
+ * report as device memory of the context's device or as managed memory (the pointer is never
+ * dereferenced to find out).
+ * Routes that need the cloud in host memory stage the buffer down and go on as the host call does
+ * (correct, and slower than the host call itself): the host octree builder (max_depth > 21 or
+ * ICP_BUILD_HOST), the host query order (config query_order = 1) and multi-device contexts, whose
+ * members each upload their replica or shard (outputs of a group are assembled on the host and
+ * copied up). */
+#define ICP_HIP_COPY_H2D 0
+#define ICP_HIP_COPY_D2H 1
+#define ICP_HIP_COPY_D2D 2
+/* HBM on the context's device (a group: its first member's), for callers without a HIP toolchain.
+ * dev_copy is synchronous: it returns when the bytes have arrived. dev_free(null) is a no-op. */
+int icp_hip_dev_alloc(icp_hip_ctx* ctx, size_t bytes, void** out);
+int icp_hip_dev_free(icp_hip_ctx* ctx, void* p);
+int icp_hip_dev_copy(icp_hip_ctx* ctx, void* dst, const void* src, size_t bytes, int dir);
+
+/* icp_hip_set_target / icp_hip_set_source from a device buffer. */
+int icp_hip_set_target_device(icp_hip_ctx* ctx, const double* d_xyz, int64_t n, int max_points, int max_depth,
+                              int rules);
+int icp_hip_set_source_device(icp_hip_ctx* ctx, const double* d_xyz, int64_t n);
+/* icp_hip_get_source / icp_hip_get_correspondences into device buffers (source size; either
+ * correspondence output may be null). */
+int icp_hip_get_source_device(icp_hip_ctx* ctx, double* d_xyz_out);
+int icp_hip_get_correspondences_device(icp_hip_ctx* ctx, int32_t* d_idx_out, double* d_dist_out);
+/* icp_hip_nn with queries and answers in device buffers (either output may be null). */
+int icp_hip_nn_device(icp_hip_ctx* ctx, const double* d_q_xyz, int64_t n, int32_t* d_idx_out, double* d_dist_out);
 
 /* Work of the reference DFS for the resident source (node entries and leaf points compared,
  * both as the reference visits them) — the V and P of the roofline byte model. */

@@ -25,6 +25,7 @@ XPORT_HOST = 2
 XPORT_CALLBACK = 3
 # icp_hip.h error codes (IcpError.code)
 OK, EINVAL, ENOMEM, EDEVICE, ERCCL, ENOTREADY, EEXCHANGE = 0, -1, -2, -3, -4, -5, -6
+COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2  # icp_hip_dev_copy directions
 DBG_SLOTS = 40
 # icp_hip.h ICP_DBG_* slot names
 DBG_NAMES = {0: "waves", 1: "overflow_waves", 2: "not_joined", 3: "not_covered", 4: "scanned_points",
@@ -172,6 +173,14 @@ SIGNATURES = {
     "icp_hip_get_source": (C.c_int, [_P, _P]),
     "icp_hip_get_correspondences": (C.c_int, [_P, _P, _P]),
     "icp_hip_nn": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "icp_hip_dev_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "icp_hip_dev_free": (C.c_int, [_P, _P]),
+    "icp_hip_dev_copy": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
+    "icp_hip_set_target_device": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "icp_hip_set_source_device": (C.c_int, [_P, _P, C.c_int64]),
+    "icp_hip_get_source_device": (C.c_int, [_P, _P]),
+    "icp_hip_get_correspondences_device": (C.c_int, [_P, _P, _P]),
+    "icp_hip_nn_device": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "icp_hip_traversal_counts": (C.c_int, [_P, _D, _D]),
     "icp_hip_target_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I32, _I32]),
     "icp_hip_last_timing": (C.c_int, [_P, _D, _D]),
@@ -235,6 +244,16 @@ SIGNATURES = {
     "icp_las_write_core_bounds": (C.c_int, [C.c_char_p, _P, C.c_int64, _P]),
     "icp_las_write_cli": (C.c_int, [C.c_char_p, _P, C.c_int64, _P, _P]),
     "icp_write_transform_report": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_int32]),
+    "icp_hip_read_las_device": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int64, C.c_int64, _P, C.POINTER(LasHeader),
+                                          C.POINTER(C.c_int64)]),
+    "icp_hip_set_target_las": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(LasHeader), C.POINTER(C.c_int64)]),
+    "icp_hip_set_source_las": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(LasHeader),
+                                         C.POINTER(C.c_int64)]),
+    "icp_hip_write_las_device": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.c_int, _P, _P, _P]),
+    "icp_hip_write_source_las": (C.c_int, [_P, C.c_char_p, C.c_int, _P, _P, _P]),
+    "icp_hip_last_las_path": (C.c_int, [_P, _I32]),
+    "icp_hip_set_las_chunk_bytes": (C.c_int, [_P, C.c_size_t]),
 }
 
 _LIB = None
@@ -421,6 +440,88 @@ class Context:
         _check(lib().icp_hip_nn(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(d)))
         return idx, d
 
+    # --- device-resident clouds (icp_hip_*_device): buffers are DeviceBuffer objects or raw
+    # device addresses (ints)
+    def device_buffer(self, nbytes: int) -> "DeviceBuffer":
+        """HBM on this context's device (icp_hip_dev_alloc)."""
+        return DeviceBuffer(self, nbytes)
+
+    def to_device(self, a: np.ndarray) -> "DeviceBuffer":
+        """A DeviceBuffer holding a copy of the array's bytes."""
+        a = np.ascontiguousarray(a)
+        buf = DeviceBuffer(self, a.nbytes)
+        buf.upload(a)
+        return buf
+
+    def set_target_device(self, d_xyz, n: int, max_points=10, max_depth=20, rules=RULES_ENGINE):
+        _check(lib().icp_hip_set_target_device(self._h, _dptr(d_xyz), n, max_points, max_depth, rules))
+        self._n_tgt = n
+
+    def set_source_device(self, d_xyz, n: int):
+        _check(lib().icp_hip_set_source_device(self._h, _dptr(d_xyz), n))
+        self.n_src = n
+
+    def get_source_device(self, d_xyz_out):
+        _check(lib().icp_hip_get_source_device(self._h, _dptr(d_xyz_out)))
+
+    def get_correspondences_device(self, d_idx_out=None, d_dist_out=None):
+        _check(lib().icp_hip_get_correspondences_device(self._h, _dptr(d_idx_out), _dptr(d_dist_out)))
+
+    def nn_device(self, d_q, n: int, d_idx_out=None, d_dist_out=None):
+        _check(lib().icp_hip_nn_device(self._h, _dptr(d_q), n, _dptr(d_idx_out), _dptr(d_dist_out)))
+
+    # --- LAS files to and from device-resident clouds (include/icp_las.h)
+    def read_las_device(self, path, rules=1, max_points=0, stride=1):
+        """Decode a LAS file into a new DeviceBuffer. Returns (buffer, n points, header)."""
+        hdr, n = LasHeader(), C.c_int64()
+        bpath = str(path).encode()
+        _check(lib().icp_hip_read_las_device(self._h, bpath, rules, max_points, stride, None, C.byref(hdr), C.byref(n)))
+        buf = DeviceBuffer(self, 24 * max(1, n.value))
+        try:
+            _check(lib().icp_hip_read_las_device(self._h, bpath, rules, max_points, stride, _dptr(buf), C.byref(hdr),
+                                                 C.byref(n)))
+        except Exception:
+            buf.free()
+            raise
+        return buf, n.value, hdr
+
+    def set_target_las(self, path, las_rules=1, max_points=0, stride=1, max_tree_points=10, max_depth=20,
+                       rules=RULES_ENGINE):
+        hdr, n = LasHeader(), C.c_int64()
+        _check(lib().icp_hip_set_target_las(self._h, str(path).encode(), las_rules, max_points, stride, max_tree_points,
+                                            max_depth, rules, C.byref(hdr), C.byref(n)))
+        self._n_tgt = n.value
+        return n.value, hdr
+
+    def set_source_las(self, path, las_rules=1, max_points=0, stride=1):
+        hdr, n = LasHeader(), C.c_int64()
+        _check(lib().icp_hip_set_source_las(self._h, str(path).encode(), las_rules, max_points, stride, C.byref(hdr),
+                                            C.byref(n)))
+        self.n_src = n.value
+        return n.value, hdr
+
+    @staticmethod
+    def _las_vec(v):
+        return None if v is None else np.ascontiguousarray(v, np.float64)
+
+    def write_las_device(self, path, d_xyz, n, flavour=1, scale=None, offset=None, bounds=None):
+        sc, of, bd = self._las_vec(scale), self._las_vec(offset), self._las_vec(bounds)
+        _check(lib().icp_hip_write_las_device(self._h, str(path).encode(), _dptr(d_xyz), n, flavour, _ptr(sc), _ptr(of),
+                                              _ptr(bd)))
+
+    def write_source_las(self, path, flavour=1, scale=None, offset=None, bounds=None):
+        sc, of, bd = self._las_vec(scale), self._las_vec(offset), self._las_vec(bounds)
+        _check(lib().icp_hip_write_source_las(self._h, str(path).encode(), flavour, _ptr(sc), _ptr(of), _ptr(bd)))
+
+    def last_las_path(self) -> int:
+        """1: the last LAS call went through the decode / encode kernels; 0: the host reader / writer."""
+        f = C.c_int32()
+        _check(lib().icp_hip_last_las_path(self._h, C.byref(f)))
+        return f.value
+
+    def set_las_chunk_bytes(self, nbytes: int):
+        _check(lib().icp_hip_set_las_chunk_bytes(self._h, nbytes))
+
     def traversal_counts(self):
         a, b = C.c_double(), C.c_double()
         _check(lib().icp_hip_traversal_counts(self._h, C.byref(a), C.byref(b)))
@@ -519,6 +620,59 @@ class Context:
         hist = (IterationRecord * max(1, history_cap))()
         rc = lib().icp_engine_run(self._h, C.byref(params), C.byref(res), hist, history_cap, None)
         return rc, res, [hist[k] for k in range(res.n_history)]
+
+
+def _dptr(b):
+    """A device address for the C-ABI: a DeviceBuffer, an int, or None."""
+    if b is None:
+        return None
+    return C.c_void_p(b.ptr if isinstance(b, DeviceBuffer) else int(b))
+
+
+class DeviceBuffer:
+    """HBM owned through a context (icp_hip_dev_alloc / _dev_copy / _dev_free): what a caller
+    without a HIP runtime of its own hands to the *_device entry points."""
+
+    def __init__(self, ctx: Context, nbytes: int):
+        self._ctx = ctx  # keep alive: the buffer is freed through it
+        self.nbytes = int(nbytes)
+        p = C.c_void_p()
+        _check(lib().icp_hip_dev_alloc(ctx.handle, self.nbytes, C.byref(p)))
+        self.ptr = p.value or 0
+
+    def upload(self, a: np.ndarray, offset: int = 0):
+        a = np.ascontiguousarray(a)
+        if offset < 0 or offset + a.nbytes > self.nbytes:
+            raise ValueError("upload past the end of the device buffer")
+        _check(lib().icp_hip_dev_copy(self._ctx.handle, C.c_void_p(self.ptr + offset), _ptr(a), a.nbytes, COPY_H2D))
+
+    def download(self, dtype=np.uint8, shape=None, offset: int = 0) -> np.ndarray:
+        """The buffer's bytes from `offset` as an array of dtype (shape: default all of them, flat)."""
+        dt = np.dtype(dtype)
+        if shape is None:
+            shape = ((self.nbytes - offset) // dt.itemsize,)
+        out = np.empty(shape, dt)
+        if offset < 0 or offset + out.nbytes > self.nbytes:
+            raise ValueError("download past the end of the device buffer")
+        _check(lib().icp_hip_dev_copy(self._ctx.handle, _ptr(out), C.c_void_p(self.ptr + offset), out.nbytes, COPY_D2H))
+        return out
+
+    def free(self):
+        if self.ptr and self._ctx.handle:
+            lib().icp_hip_dev_free(self._ctx.handle, C.c_void_p(self.ptr))
+        self.ptr = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class Session:

@@ -3,6 +3,7 @@
 #include <cfloat>
 #include <cstddef>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "icp_ctx_internal.h"
@@ -87,15 +88,52 @@ static void keep_tree_info(icp_hip_ctx* c, const Tree& t, int64_t n_nodes) {
   c->levels = t.max_inner_depth + 1 > 0 ? t.max_inner_depth + 1 : 1;
 }
 
-extern "C" {
+// --- device-pointer entry points (icp_hip_*_device): the caller's buffer is checked by its
+// attributes alone (never dereferenced on the host), then handed to the same device core the host
+// variants run after their upload.
 
-int icp_hip_set_target(icp_hip_ctx* c, const double* xyz, int64_t n, int max_points, int max_depth, int rules) {
-  if (!c || (!xyz && n > 0)) return fail(ICP_HIP_EINVAL, "null argument");
-  if (c->group) return n <= 0 ? fail(ICP_HIP_EINVAL, "empty target cloud (icpengine.cpp:31-34 rejects it)")
-                             : group_set_target(c, xyz, n, max_points, max_depth, rules);
-  if (n <= 0) return fail(ICP_HIP_EINVAL, "empty target cloud (icpengine.cpp:31-34 rejects it)");
-  if (max_depth < 0 || max_depth > 60) return fail(ICP_HIP_EINVAL, "max_depth out of range [0, 60]");
-  if (n > (int64_t)0x7fffffff) return fail(ICP_HIP_EINVAL, "target size out of range (int32 indices, as the reference)");
+// A buffer a kernel of this context may read or write: device memory of the context's device, or
+// managed memory. A group's host-staged routes only copy it, so any device's memory will do.
+int check_device_ptr(const icp_hip_ctx* c, const void* p, const char* what, unsigned align) {
+  if (!p) return fail(ICP_HIP_EINVAL, std::string(what) + ": null device pointer");
+  if (reinterpret_cast<uintptr_t>(p) % align != 0)
+    return fail(ICP_HIP_EINVAL, std::string(what) + ": pointer not " + std::to_string(align) + "-byte aligned");
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ICP_HIP_EINVAL, std::string(what) + ": not a device pointer (" + hipGetErrorString(e) + ")");
+  }
+  if (at.type == hipMemoryTypeManaged) return ICP_HIP_OK;
+  if (at.type != hipMemoryTypeDevice) return fail(ICP_HIP_EINVAL, std::string(what) + ": host memory, not a device pointer");
+  if (!c->group && at.device != c->device)
+    return fail(ICP_HIP_EINVAL, std::string(what) + ": device memory of another device than the context's");
+  return ICP_HIP_OK;
+}
+
+// The host-staged routes of the device variants: the caller's buffer through host memory.
+template <typename T>
+static hipError_t stage_down(const icp_hip_ctx* c, std::vector<T>* h, const T* d, size_t count) {
+  h->resize(count);
+  if (count == 0) return hipSuccess;
+  if (c->group) return hipMemcpy(h->data(), d, count * sizeof(T), hipMemcpyDeviceToHost);
+  hipError_t e = hipMemcpyAsync(h->data(), d, count * sizeof(T), hipMemcpyDeviceToHost, c->stream);
+  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
+
+template <typename T>
+static hipError_t stage_up(const icp_hip_ctx* c, T* d, const std::vector<T>& h) {
+  if (h.empty()) return hipSuccess;
+  if (c->group) return hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+  hipError_t e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
+  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
+
+// set_target after the argument checks, from a host cloud (xyz) or a device cloud (d_in), one of
+// them null. The device builder reads d_in in place; the host builder gets it staged down.
+static int set_target_core(icp_hip_ctx* c, const double* xyz, const double* d_in, int64_t n, int max_points,
+                           int max_depth, int rules) {
   HIP_TRY(hipSetDevice(c->device));
   free_target(c);
   HIP_TRY(reset_band(c));
@@ -103,23 +141,30 @@ int icp_hip_set_target(icp_hip_ctx* c, const double* xyz, int64_t n, int max_poi
   HIP_TRY(hipEventRecord(e0, c->stream));
   const bool on_device = max_depth <= kGpuBuildMaxDepth && c->cfg.octree_builder == ICP_BUILD_AUTO;
   if (on_device) {
-    // device build straight from the uploaded AoS cloud (octree_gpu.hip)
+    // device build straight from the AoS cloud in HBM (octree_gpu.hip): the caller's, or the upload
     double* d_xyz = nullptr;
-    HIP_TRY(dalloc(&d_xyz, 3 * (size_t)n));
-    hipError_t e = hipMemcpyAsync(d_xyz, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-      dfree(d_xyz);
-      return fail(ICP_HIP_EDEVICE, std::string("set_target upload: ") + hipGetErrorString(e));
+    if (!d_in) {
+      HIP_TRY(dalloc(&d_xyz, 3 * (size_t)n));
+      hipError_t e = hipMemcpyAsync(d_xyz, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
+      if (e != hipSuccess) {
+        dfree(d_xyz);
+        return fail(ICP_HIP_EDEVICE, std::string("set_target upload: ") + hipGetErrorString(e));
+      }
     }
     GpuOctree t;
     std::string why;
-    const int rc = gpu_build_octree(d_xyz, n, max_points, max_depth, c->stream, &t, &why);
+    const int rc = gpu_build_octree(d_in ? d_in : d_xyz, n, max_points, max_depth, c->stream, &t, &why);
     dfree(d_xyz);
     if (rc != 0) return fail(rc == 1 ? ICP_HIP_EINVAL : rc == -2 ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, why);
     c->nodes = t.nodes;
     c->pts = t.pts;
     keep_tree_info(c, t, t.n_nodes);
   } else {
+    std::vector<double> staged;
+    if (!xyz) {
+      HIP_TRY(stage_down(c, &staged, d_in, 3 * (size_t)n));
+      xyz = staged.data();
+    }
     FlatOctree t;
     const char* why = nullptr;
     if (!build_flat_octree(xyz, n, max_points, max_depth, &t, &why)) return fail(ICP_HIP_EINVAL, why ? why : "bad target");
@@ -169,6 +214,65 @@ int icp_hip_set_target(icp_hip_ctx* c, const double* xyz, int64_t n, int max_poi
   c->wc_gen++;  // cached candidate lists name points of the previous tree
   c->have_results = false;
   return ICP_HIP_OK;
+}
+
+extern "C" {
+
+// HBM for the device entry points, so that a C caller needs no HIP toolchain. A group allocates on
+// its first member's device.
+int icp_hip_dev_alloc(icp_hip_ctx* c, size_t bytes, void** out) {
+  if (!c || !out) return fail(ICP_HIP_EINVAL, "null argument");
+  *out = nullptr;
+  HIP_TRY(hipSetDevice(c->group ? group_member(c, 0)->device : c->device));
+  HIP_TRY(hipMalloc(out, bytes ? bytes : 1));
+  return ICP_HIP_OK;
+}
+
+int icp_hip_dev_free(icp_hip_ctx* c, void* p) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null argument");
+  if (!p) return ICP_HIP_OK;
+  HIP_TRY(hipSetDevice(c->group ? group_member(c, 0)->device : c->device));
+  HIP_TRY(hipFree(p));
+  return ICP_HIP_OK;
+}
+
+int icp_hip_dev_copy(icp_hip_ctx* c, void* dst, const void* src, size_t bytes, int dir) {
+  if (!c || ((!dst || !src) && bytes > 0)) return fail(ICP_HIP_EINVAL, "null argument");
+  if (dir != ICP_HIP_COPY_H2D && dir != ICP_HIP_COPY_D2H && dir != ICP_HIP_COPY_D2D)
+    return fail(ICP_HIP_EINVAL, "dev_copy: unknown direction");
+  if (bytes == 0) return ICP_HIP_OK;
+  const hipMemcpyKind kind = dir == ICP_HIP_COPY_H2D   ? hipMemcpyHostToDevice
+                             : dir == ICP_HIP_COPY_D2H ? hipMemcpyDeviceToHost
+                                                       : hipMemcpyDeviceToDevice;
+  icp_hip_ctx* m = c->group ? group_member(c, 0) : c;
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  return ICP_HIP_OK;
+}
+
+int icp_hip_set_target(icp_hip_ctx* c, const double* xyz, int64_t n, int max_points, int max_depth, int rules) {
+  if (!c || (!xyz && n > 0)) return fail(ICP_HIP_EINVAL, "null argument");
+  if (c->group) return n <= 0 ? fail(ICP_HIP_EINVAL, "empty target cloud (icpengine.cpp:31-34 rejects it)")
+                             : group_set_target(c, xyz, n, max_points, max_depth, rules);
+  if (n <= 0) return fail(ICP_HIP_EINVAL, "empty target cloud (icpengine.cpp:31-34 rejects it)");
+  if (max_depth < 0 || max_depth > 60) return fail(ICP_HIP_EINVAL, "max_depth out of range [0, 60]");
+  if (n > (int64_t)0x7fffffff) return fail(ICP_HIP_EINVAL, "target size out of range (int32 indices, as the reference)");
+  return set_target_core(c, xyz, nullptr, n, max_points, max_depth, rules);
+}
+
+int icp_hip_set_target_device(icp_hip_ctx* c, const double* d_xyz, int64_t n, int max_points, int max_depth, int rules) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null argument");
+  if (n <= 0) return fail(ICP_HIP_EINVAL, "empty target cloud (icpengine.cpp:31-34 rejects it)");
+  if (max_depth < 0 || max_depth > 60) return fail(ICP_HIP_EINVAL, "max_depth out of range [0, 60]");
+  if (n > (int64_t)0x7fffffff) return fail(ICP_HIP_EINVAL, "target size out of range (int32 indices, as the reference)");
+  if (const int rc = check_device_ptr(c, d_xyz, "set_target_device")) return rc;
+  if (c->group) {  // every member uploads its replica from host memory
+    std::vector<double> staged;
+    HIP_TRY(stage_down(c, &staged, d_xyz, 3 * (size_t)n));
+    return group_set_target(c, staged.data(), n, max_points, max_depth, rules);
+  }
+  return set_target_core(c, nullptr, d_xyz, n, max_points, max_depth, rules);
 }
 
 int icp_hip_target_build_info(icp_hip_ctx* c, int32_t* on_device, double* build_ms) {
@@ -235,9 +339,10 @@ int icp_hip_target_info(icp_hip_ctx* c, int64_t* n_nodes, int64_t* n_leaves, int
   return ICP_HIP_OK;
 }
 
-int icp_hip_set_source(icp_hip_ctx* c, const double* xyz, int64_t n) {
-  if (!c || (!xyz && n > 0) || n < 0) return fail(ICP_HIP_EINVAL, "bad source arguments");
-  if (c->group) return group_set_source(c, xyz, n);
+// set_source after the argument checks, from a host cloud (xyz) or a device cloud (d_in), one of
+// them null when n > 0. The device query order and the gather read d_in in place; the host query
+// order gets it staged down.
+static int set_source_core(icp_hip_ctx* c, const double* xyz, const double* d_in, int64_t n) {
   // the wave search addresses per-query arrays by 32-bit byte offsets (nn_device.h qat): < 2^29
   // points per shard (12 GB of coordinates; a larger cloud is sharded over a device group)
   if (n >= ((int64_t)1 << 29)) return fail(ICP_HIP_EINVAL, "source shard of 2^29 points or more");
@@ -277,26 +382,54 @@ int icp_hip_set_source(icp_hip_ctx* c, const double* xyz, int64_t n) {
   if (n == 0) return ICP_HIP_OK;
   // Spatially compact query order (kd buckets of 64 = one wave): on the device from the uploaded
   // cloud (query_order_gpu.hip), or on the host (config query_order = 1)
-  double* aos = nullptr;
-  hipError_t e = dalloc(&aos, 3 * (size_t)n);
-  if (e == hipSuccess) e = hipMemcpyAsync(aos, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
+  double* scratch = nullptr;
+  const double* aos = d_in;
+  hipError_t e = hipSuccess;
+  if (!d_in) {
+    e = dalloc(&scratch, 3 * (size_t)n);
+    if (e == hipSuccess) e = hipMemcpyAsync(scratch, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
+    aos = scratch;
+  }
   if (e == hipSuccess) {
     if (c->cfg.query_order == 0) {
       e = gpu_kd_query_order(aos, n, 8, c->perm, c->stream);
     } else {
+      std::vector<double> staged;
+      if (!xyz) {
+        e = stage_down(c, &staged, d_in, 3 * (size_t)n);
+        xyz = staged.data();
+      }
       std::vector<int32_t> perm;
-      kd_query_order(xyz, n, 8, &perm);
-      e = hipMemcpyAsync(c->perm, perm.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) kd_query_order(xyz, n, 8, &perm);
+      if (e == hipSuccess) e = hipMemcpyAsync(c->perm, perm.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host order is read by the copy
     }
   }
   if (e == hipSuccess) e = launch_gather_deinterleave(aos, c->perm, c->x, c->y, c->z, n, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(aos);
+  dfree(scratch);
   if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("set_source: ") + hipGetErrorString(e));
   c->have_results = false;
   c->have_prev = false;
   return ICP_HIP_OK;
+}
+
+int icp_hip_set_source(icp_hip_ctx* c, const double* xyz, int64_t n) {
+  if (!c || (!xyz && n > 0) || n < 0) return fail(ICP_HIP_EINVAL, "bad source arguments");
+  if (c->group) return group_set_source(c, xyz, n);
+  return set_source_core(c, xyz, nullptr, n);
+}
+
+int icp_hip_set_source_device(icp_hip_ctx* c, const double* d_xyz, int64_t n) {
+  if (!c || n < 0) return fail(ICP_HIP_EINVAL, "bad source arguments");
+  if (const int rc = check_device_ptr(c, d_xyz, "set_source_device")) return rc;
+  if (c->group) {  // the shards are cut and uploaded from host memory
+    if (n > (int64_t)0x7fffffff) return fail(ICP_HIP_EINVAL, "set_source: 2^31 points or more (int32 query order)");
+    std::vector<double> staged;
+    HIP_TRY(stage_down(c, &staged, d_xyz, 3 * (size_t)n));
+    return group_set_source(c, staged.data(), n);
+  }
+  return set_source_core(c, nullptr, d_xyz, n);
 }
 
 int icp_hip_apply(icp_hip_ctx* c, const double* T) {
@@ -324,6 +457,24 @@ int icp_hip_get_source(icp_hip_ctx* c, double* xyz_out) {
   return ICP_HIP_OK;
 }
 
+int icp_hip_get_source_device(icp_hip_ctx* c, double* d_xyz_out) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null argument");
+  if (const int rc = check_device_ptr(c, d_xyz_out, "get_source_device")) return rc;
+  if (c->group) {  // the members' shards are put back in the caller's order on the host
+    std::vector<double> staged(3 * (size_t)group_n_src(c));
+    const int rc = group_get_source(c, staged.data());
+    if (rc != ICP_HIP_OK) return rc;
+    HIP_TRY(stage_up(c, d_xyz_out, staged));
+    return ICP_HIP_OK;
+  }
+  if (c->n_src == 0) return ICP_HIP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipError_t e = launch_scatter_aos(c->perm, c->x, c->y, c->z, d_xyz_out, c->n_src, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("get_source_device: ") + hipGetErrorString(e));
+  return ICP_HIP_OK;
+}
+
 int icp_hip_get_correspondences(icp_hip_ctx* c, int32_t* idx_out, double* dist_out) {
   if (!c) return fail(ICP_HIP_EINVAL, "null argument");
   if (c->group) return group_get_correspondences(c, idx_out, dist_out);
@@ -345,11 +496,34 @@ int icp_hip_get_correspondences(icp_hip_ctx* c, int32_t* idx_out, double* dist_o
   return ICP_HIP_OK;
 }
 
-int icp_hip_nn(icp_hip_ctx* c, const double* q, int64_t n, int32_t* idx_out, double* dist_out) {
-  if (!c || n < 0 || (n > 0 && !q)) return fail(ICP_HIP_EINVAL, "bad arguments");
-  if (c->group) return icp_hip_nn(group_member(c, 0), q, n, idx_out, dist_out);  // the replicated octree
-  if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
-  if (n == 0) return ICP_HIP_OK;
+int icp_hip_get_correspondences_device(icp_hip_ctx* c, int32_t* d_idx_out, double* d_dist_out) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null argument");
+  if (d_idx_out)  // int32 indices: 4-byte aligned
+    if (const int rc = check_device_ptr(c, d_idx_out, "get_correspondences_device", 4)) return rc;
+  if (d_dist_out)
+    if (const int rc = check_device_ptr(c, d_dist_out, "get_correspondences_device")) return rc;
+  if (c->group) {
+    const size_t n = (size_t)group_n_src(c);
+    std::vector<int32_t> idx(d_idx_out ? n : 0);
+    std::vector<double> d(d_dist_out ? n : 0);
+    const int rc = group_get_correspondences(c, d_idx_out ? idx.data() : nullptr, d_dist_out ? d.data() : nullptr);
+    if (rc != ICP_HIP_OK) return rc;
+    HIP_TRY(stage_up(c, d_idx_out, idx));
+    HIP_TRY(stage_up(c, d_dist_out, d));
+    return ICP_HIP_OK;
+  }
+  if (!c->have_results) return fail(ICP_HIP_ENOTREADY, "no iteration has run on this source");
+  if (c->n_src == 0 || (!d_idx_out && !d_dist_out)) return ICP_HIP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipError_t e = launch_scatter_corr(c->perm, c->pos, c->pts, d_idx_out, c->dist, d_dist_out, c->n_src, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("get_correspondences_device: ") + hipGetErrorString(e));
+  return ICP_HIP_OK;
+}
+
+// nn after the argument checks. dev = false: q and the outputs are host buffers (uploaded, searched,
+// downloaded); dev = true: they are the caller's device buffers, read and written in place.
+static int nn_core(icp_hip_ctx* c, bool dev, const double* q, int64_t n, int32_t* idx_out, double* dist_out) {
   // the wave search addresses per-query arrays by 32-bit byte offsets (nn_device.h qat): launches
   // of fewer than 2^29 queries, so larger sets go in slices (the answers are per query)
   constexpr int64_t kSlice = (int64_t)1 << 28;
@@ -357,7 +531,7 @@ int icp_hip_nn(icp_hip_ctx* c, const double* q, int64_t n, int32_t* idx_out, dou
     unsigned int lists[3] = {0, 0, 0};
     for (int64_t off = 0; off < n; off += kSlice) {
       const int64_t m = n - off < kSlice ? n - off : kSlice;
-      const int rc = icp_hip_nn(c, q + 3 * off, m, idx_out ? idx_out + off : nullptr, dist_out ? dist_out + off : nullptr);
+      const int rc = nn_core(c, dev, q + 3 * off, m, idx_out ? idx_out + off : nullptr, dist_out ? dist_out + off : nullptr);
       if (rc != ICP_HIP_OK) return rc;
       for (int k = 0; k < 3; k++) lists[k] += c->last_lists[k];
     }
@@ -365,13 +539,15 @@ int icp_hip_nn(icp_hip_ctx* c, const double* q, int64_t n, int32_t* idx_out, dou
     return ICP_HIP_OK;
   }
   HIP_TRY(hipSetDevice(c->device));
-  double *aos = nullptr, *x = nullptr, *y = nullptr, *z = nullptr, *d = nullptr, *dd = nullptr;
+  double *up = nullptr, *x = nullptr, *y = nullptr, *z = nullptr, *d = nullptr, *dd = nullptr;
   int32_t *pos = nullptr, *di = nullptr;
   hipError_t e = hipSuccess;
-  if ((e = dalloc(&aos, 3 * (size_t)n)) == hipSuccess && (e = dalloc(&x, n)) == hipSuccess &&
+  if ((dev || (e = dalloc(&up, 3 * (size_t)n)) == hipSuccess) && (e = dalloc(&x, n)) == hipSuccess &&
       (e = dalloc(&y, n)) == hipSuccess && (e = dalloc(&z, n)) == hipSuccess && (e = dalloc(&d, n)) == hipSuccess &&
-      (e = dalloc(&dd, n)) == hipSuccess && (e = dalloc(&pos, n)) == hipSuccess && (e = dalloc(&di, n)) == hipSuccess) {
-    e = hipMemcpyAsync(aos, q, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
+      (dev || (e = dalloc(&dd, n)) == hipSuccess) && (e = dalloc(&pos, n)) == hipSuccess &&
+      (dev || (e = dalloc(&di, n)) == hipSuccess)) {
+    if (!dev) e = hipMemcpyAsync(up, q, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
+    const double* aos = dev ? q : up;
     if (e == hipSuccess) e = launch_deinterleave(aos, x, y, z, n, c->stream);
     NNLaunch a = base_launch(c);
     a.x = x;
@@ -402,14 +578,50 @@ int icp_hip_nn(icp_hip_ctx* c, const double* q, int64_t n, int32_t* idx_out, dou
     c->last_lists[2] = lists4[2];
     dfree(fbl);
     dfree(fbu);
-    if (e == hipSuccess) e = launch_scatter_corr(nullptr, pos, c->pts, di, d, dd, n, c->stream);
-    if (e == hipSuccess && idx_out) e = hipMemcpyAsync(idx_out, di, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && dist_out) e = hipMemcpyAsync(dist_out, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream);
+    if (dev) {
+      // straight into the caller's buffers (either may be null)
+      if (e == hipSuccess && (idx_out || dist_out)) e = launch_scatter_corr(nullptr, pos, c->pts, idx_out, d, dist_out, n, c->stream);
+    } else {
+      if (e == hipSuccess) e = launch_scatter_corr(nullptr, pos, c->pts, di, d, dd, n, c->stream);
+      if (e == hipSuccess && idx_out) e = hipMemcpyAsync(idx_out, di, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess && dist_out) e = hipMemcpyAsync(dist_out, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   }
-  dfree(aos); dfree(x); dfree(y); dfree(z); dfree(d); dfree(dd); dfree(pos); dfree(di);
+  dfree(up); dfree(x); dfree(y); dfree(z); dfree(d); dfree(dd); dfree(pos); dfree(di);
   if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, std::string("nn: ") + hipGetErrorString(e));
   return ICP_HIP_OK;
+}
+
+int icp_hip_nn(icp_hip_ctx* c, const double* q, int64_t n, int32_t* idx_out, double* dist_out) {
+  if (!c || n < 0 || (n > 0 && !q)) return fail(ICP_HIP_EINVAL, "bad arguments");
+  if (c->group) return icp_hip_nn(group_member(c, 0), q, n, idx_out, dist_out);  // the replicated octree
+  if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
+  if (n == 0) return ICP_HIP_OK;
+  return nn_core(c, false, q, n, idx_out, dist_out);
+}
+
+int icp_hip_nn_device(icp_hip_ctx* c, const double* d_q, int64_t n, int32_t* d_idx_out, double* d_dist_out) {
+  if (!c || n < 0) return fail(ICP_HIP_EINVAL, "bad arguments");
+  if (const int rc = check_device_ptr(c, d_q, "nn_device")) return rc;
+  if (d_idx_out)
+    if (const int rc = check_device_ptr(c, d_idx_out, "nn_device", 4)) return rc;
+  if (d_dist_out)
+    if (const int rc = check_device_ptr(c, d_dist_out, "nn_device")) return rc;
+  if (c->group) {  // the first member's replica, through host memory (the buffers may be another device's)
+    std::vector<double> hq;
+    HIP_TRY(stage_down(c, &hq, d_q, 3 * (size_t)n));
+    std::vector<int32_t> idx(d_idx_out ? (size_t)n : 0);
+    std::vector<double> d(d_dist_out ? (size_t)n : 0);
+    const int rc = icp_hip_nn(group_member(c, 0), hq.data(), n, d_idx_out ? idx.data() : nullptr, d_dist_out ? d.data() : nullptr);
+    if (rc != ICP_HIP_OK) return rc;
+    HIP_TRY(stage_up(c, d_idx_out, idx));
+    HIP_TRY(stage_up(c, d_dist_out, d));
+    return ICP_HIP_OK;
+  }
+  if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
+  if (n == 0) return ICP_HIP_OK;
+  return nn_core(c, true, d_q, n, d_idx_out, d_dist_out);
 }
 
 int icp_hip_traversal_counts(icp_hip_ctx* c, double* mean_entries, double* mean_points) {

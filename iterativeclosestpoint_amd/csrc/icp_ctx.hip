@@ -190,6 +190,7 @@ void icp_hip_destroy(icp_hip_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   prewalk_destroy(c);
+  las_destroy(c);
   free_source(c);
   free_target(c);
   dfree(c->it);

@@ -116,6 +116,11 @@ struct icp_hip_ctx {
   // --- prewalk (ctx_prewalk.cpp)
   Prewalk pw;
 
+  // --- LAS records decoded / encoded on the device (ctx_las.cpp): staging buffers, made at first use
+  struct LasIo* las = nullptr;
+  int las_device_path = -1;      // icp_hip_last_las_path: 1 kernels, 0 host reader / writer, -1 none yet
+  size_t las_chunk_bytes = 8u << 20;  // icp_hip_set_las_chunk_bytes
+
   // --- multi-device context (icp_hip_create_multi): the member contexts and their driver threads
   // (icp_group.cpp); the single-device fields above are then unused
   struct DeviceGroup* group = nullptr;
@@ -127,6 +132,10 @@ void free_source(icp_hip_ctx* c);
 // The search launch over the resident target with this context's configuration; the caller
 // fills the query arrays and the lists.
 icp::NNLaunch base_launch(const icp_hip_ctx* c);
+// The argument check of the device-pointer entry points: ICP_HIP_EINVAL (with a message naming
+// `what`) unless p is non-null, aligned, and device memory of the context's device or managed
+// memory by hipPointerGetAttributes. Never dereferences p.
+int check_device_ptr(const icp_hip_ctx* c, const void* p, const char* what, unsigned align = 8);
 
 // --- ctx_prewalk.cpp
 // The prewalk's one safety rule: whatever frees, regenerates or reads the record buffers (wc_box,
@@ -148,6 +157,9 @@ int prewalk_join(icp_hip_ctx* c, hipStream_t s);
 // overwrites the transform (LoopDev::core.T) that the prewalk's lead reads while it would run.
 bool prewalk_arm(icp_hip_ctx* c, icp::NNLaunch& a, const icp::LoopDev* loop, bool apply);
 int prewalk_launch(icp_hip_ctx* c, const icp::NNLaunch& a);  // after launch_nn of an armed iterate
+
+// --- ctx_las.cpp
+void las_destroy(icp_hip_ctx* c);  // the staging buffers released (icp_hip_destroy)
 
 // --- ctx_iterate.cpp
 int32_t* wide_list(int32_t* fbl, int64_t n);  // the wide pass's list inside fb_list (3 n + 64 ints)
@@ -194,3 +206,4 @@ int group_synchronize(icp_hip_ctx* c);
 int group_set_prewalk(icp_hip_ctx* c, double look_ahead);
 int group_inject_failure(icp_hip_ctx* c, int member, int where);
 icp_hip_ctx* group_member(icp_hip_ctx* c, int k);
+int64_t group_n_src(icp_hip_ctx* c);  // points of the last set_source, all members

@@ -173,6 +173,8 @@ void group_destroy(icp_hip_ctx* c) {
 
 icp_hip_ctx* group_member(icp_hip_ctx* c, int k) { return c->group->members[k]; }
 
+int64_t group_n_src(icp_hip_ctx* c) { return c->group->n_src; }
+
 int group_set_target(icp_hip_ctx* c, const double* xyz, int64_t n, int max_points, int max_depth, int rules) {
   // every device builds the same octree from the same cloud (a replica each)
   return for_members(c->group, [&](int, icp_hip_ctx* m) {

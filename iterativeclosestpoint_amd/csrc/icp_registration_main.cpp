@@ -5,10 +5,16 @@
 //
 //   icp_registration [--source Scan_096_origin.las] [--target Scannew_099.las]
 //                    [--sample-rate 50] [--max-iters 20] [--tolerance 1e-2]
-//                    [--outdir .] [--device 0 | --devices 0,1,...] [--pause]
+//                    [--outdir .] [--device 0 | --devices 0,1,...] [--device-io] [--pause]
 //
 // --devices runs one registration over several GPUs of this process (icp_cli_icp_devices: the
 // source sharded over them, the octree replicated, RCCL all-gathers per iteration).
+//
+// --device-io keeps both clouds resident on the GPU from file to file: the LAS records are decoded
+// and sampled by kernels (icp_hip_set_source_las, icp_hip_read_las_device), the registration runs
+// on the resident clouds and the four LAS outputs are encoded on the device
+// (icp_hip_write_source_las, icp_hip_write_las_device). The same five files byte for byte; one
+// GPU only (with --devices of more than one it is a usage error).
 //
 // Exit code 255 (the reference's `return -1`) when an input cannot be read.
 #include <cstdio>
@@ -32,13 +38,14 @@ struct Args {
   double tolerance = 1e-2;                      // :901
   std::string outdir = ".";
   std::vector<int> devices{0};
+  bool device_io = false;
   bool pause = false;
 };
 
 [[noreturn]] void usage(const char* prog, int code) {
   std::fprintf(code ? stderr : stdout,
                "usage: %s [--source F] [--target F] [--sample-rate N] [--max-iters N] [--tolerance X]\n"
-               "          [--outdir D] [--device N | --devices N,M,...] [--pause]\n",
+               "          [--outdir D] [--device N | --devices N,M,...] [--device-io] [--pause]\n",
                prog);
   std::exit(code);
 }
@@ -73,6 +80,7 @@ Args parse(int argc, char** argv) {
         p = q + 1;
       }
     }
+    else if (k == "--device-io") a.device_io = true;
     else if (k == "--pause") a.pause = true;
     else if (k == "-h" || k == "--help") usage(argv[0], 0);
     else usage(argv[0], 2);
@@ -80,6 +88,10 @@ Args parse(int argc, char** argv) {
   if (a.sample_rate < 1) {
     std::fprintf(stderr, "--sample-rate must be >= 1\n");
     std::exit(2);
+  }
+  if (a.device_io && a.devices.size() > 1) {
+    std::fprintf(stderr, "--device-io runs on one GPU (clouds resident across a device group: not supported)\n");
+    usage(argv[0], 2);
   }
   return a;
 }
@@ -104,11 +116,102 @@ int fail(const Args& a, const char* msg) {
 
 std::string out_path(const Args& a, const char* name) { return a.outdir + "/" + name; }
 
+void print_transform(const double R[9], const double t[3]) {
+  std::cout << "\n========== transform ==========" << std::endl << "R:" << std::endl;
+  for (int i = 0; i < 3; i++)
+    std::cout << "  [" << R[3 * i] << ", " << R[3 * i + 1] << ", " << R[3 * i + 2] << "]" << std::endl;
+  std::cout << "\nt:\n  [" << t[0] << ", " << t[1] << ", " << t[2] << "]" << std::endl;
+  std::cout << "===============================" << std::endl;
+}
+
+void print_cloud(int64_t n, const icp_las_header& hdr) {
+  std::cout << "  " << n << " points, scale (" << hdr.scale[0] << ", " << hdr.scale[1] << ", " << hdr.scale[2]
+            << "), offset (" << hdr.offset[0] << ", " << hdr.offset[1] << ", " << hdr.offset[2] << ")" << std::endl;
+}
+
+// --device-io: the default flow's steps on clouds that stay in HBM (one context; the same files).
+int run_device_io(const Args& a) {
+  icp_hip_ctx* ctx = nullptr;
+  void* d_tgt = nullptr;
+  auto bail = [&](const char* msg) {
+    std::cerr << msg << ": " << icp_hip_last_error() << std::endl;
+    if (ctx) (void)icp_hip_dev_free(ctx, d_tgt);
+    icp_hip_destroy(ctx);
+    return fail(a, msg);
+  };
+  if (icp_hip_create(&ctx, a.devices[0]) != ICP_HIP_OK) return bail("cannot create the GPU context");
+
+  // Read + stride down-sampling in one pass per file; readLASFile rejects an empty file (:377).
+  icp_las_header hs{}, ht{};
+  int64_t ns = 0, nt = 0;
+  std::cout << "\nsource: " << a.source << std::endl << "  reading " << a.source << std::endl;
+  if (icp_hip_set_source_las(ctx, a.source.c_str(), ICP_LAS_CLI, 0, a.sample_rate, &hs, &ns) != ICP_HIP_OK || ns <= 0)
+    return bail("cannot read the source point cloud");
+  print_cloud((int64_t)hs.num_points, hs);
+  std::cout << "\ntarget: " << a.target << std::endl << "  reading " << a.target << std::endl;
+  // the decoded target stays in a buffer of ours: the octree is built from it and both target files written
+  if (icp_hip_read_las_device(ctx, a.target.c_str(), ICP_LAS_CLI, 0, a.sample_rate, nullptr, &ht, &nt) != ICP_HIP_OK ||
+      nt <= 0 || icp_hip_dev_alloc(ctx, 3 * sizeof(double) * (size_t)nt, &d_tgt) != ICP_HIP_OK ||
+      icp_hip_read_las_device(ctx, a.target.c_str(), ICP_LAS_CLI, 0, a.sample_rate, static_cast<double*>(d_tgt), &ht,
+                              &nt) != ICP_HIP_OK)
+    return bail("cannot read the target point cloud");
+  print_cloud((int64_t)ht.num_points, ht);
+  std::cout << "\ndown-sampling (1/" << a.sample_rate << ")..." << std::endl;
+  std::cout << "source: " << ns << " points\ntarget: " << nt << " points" << std::endl;
+
+  // both sampled clouds carry the SOURCE's scale/offset (:862-876)
+  if (icp_hip_write_source_las(ctx, out_path(a, "sampled_source.las").c_str(), ICP_LAS_CLI, hs.scale, hs.offset, nullptr) !=
+          ICP_HIP_OK ||
+      icp_hip_write_las_device(ctx, out_path(a, "sampled_target.las").c_str(), static_cast<double*>(d_tgt), nt, ICP_LAS_CLI,
+                               hs.scale, hs.offset, nullptr) != ICP_HIP_OK)
+    return bail("cannot write the sampled clouds");
+
+  std::cout << "\nparameters: max iterations=" << a.max_iters << ", tolerance=" << a.tolerance << std::endl;
+  // ICP() (icp_cli_icp_devices) on the resident clouds: the CLI's octree (10 points, depth 20) and rules
+  icp_params p;
+  icp_params_default(&p);
+  p.max_iterations = a.max_iters;
+  p.tolerance = a.tolerance;
+  p.rules = ICP_RULES_CLI;
+  const int cap = a.max_iters > 0 ? a.max_iters : 1;
+  std::vector<icp_iteration_record> hist((size_t)cap);
+  icp_result res;
+  if (icp_hip_set_target_device(ctx, static_cast<double*>(d_tgt), nt, 10, 20, ICP_RULES_CLI) != ICP_HIP_OK)
+    return bail("registration failed");
+  const int rc = icp_engine_run(ctx, &p, &res, hist.data(), cap, nullptr);
+  if (rc != ICP_HIP_OK) {
+    std::cerr << "ICP failed (" << rc << ")";
+    return bail("registration failed");
+  }
+  std::vector<double> transforms((size_t)cap * 16);
+  int32_t n_tr = 0;
+  for (int32_t k = 0; k < res.n_history; k++) {
+    if (!hist[k].has_transform) continue;
+    if (n_tr < cap) std::memcpy(&transforms[16 * (size_t)n_tr], hist[k].transform, 16 * sizeof(double));
+    n_tr++;
+  }
+  print_transform(res.final_R, res.final_t);
+
+  if (icp_hip_write_source_las(ctx, out_path(a, "registered_source.las").c_str(), ICP_LAS_CLI, hs.scale, hs.offset,
+                               nullptr) != ICP_HIP_OK ||
+      icp_hip_write_las_device(ctx, out_path(a, "registered_target.las").c_str(), static_cast<double*>(d_tgt), nt,
+                               ICP_LAS_CLI, hs.scale, hs.offset, nullptr) != ICP_HIP_OK ||
+      icp_write_transform_report(out_path(a, "icp_transformation.txt").c_str(), res.final_R, res.final_t, transforms.data(),
+                                 n_tr < cap ? n_tr : cap) != 0)
+    return bail("cannot write the results");
+  (void)icp_hip_dev_free(ctx, d_tgt);
+  icp_hip_destroy(ctx);
+  std::cout << "\ndone: registered_source.las, registered_target.las, icp_transformation.txt" << std::endl;
+  if (a.pause) std::cin.get();
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   const Args a = parse(argc, argv);
   std::cout << "=== ICP point-cloud fine registration (MI355X) ===" << std::endl;
+  if (a.device_io) return run_device_io(a);
 
   std::vector<double> src, tgt;
   icp_las_header hs{}, ht{};

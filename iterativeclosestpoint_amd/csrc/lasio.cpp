@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/icp_las.h"
+#include "las_format.h"
 
 namespace {
 
@@ -39,6 +40,56 @@ int parse_header(const char* h, int rules, icp_las_header* out) {
 }
 
 }  // namespace
+
+namespace icp {
+
+// The 227-byte headers of the two writers (las_format.h): LASIO::writeLAS ...
+void las_header_core(char h[227], uint32_t n, const double mn[3], const double mx[3]) {
+  std::memset(h, 0, 227);
+  std::memcpy(h, "LASF", 4);
+  h[24] = 1;
+  h[25] = 2;
+  wr<uint16_t>(h + 94, 227);
+  wr<uint32_t>(h + 96, 227);
+  h[104] = 0;
+  wr<uint16_t>(h + 105, 20);
+  wr<uint32_t>(h + 107, n);
+  for (int a = 0; a < 3; a++) {
+    wr<double>(h + 131 + 8 * a, 0.001);
+    wr<double>(h + 155 + 8 * a, mn[a]);
+    wr<double>(h + 179 + 16 * a, mx[a]);
+    wr<double>(h + 187 + 16 * a, mn[a]);
+  }
+}
+
+// ... and saveResultAsLAS
+void las_header_cli(char h[227], uint32_t n, const double scale[3], const double offset[3], const double mn[3],
+                    const double mx[3]) {
+  std::memset(h, 0, 227);
+  std::memcpy(h, "LASF", 4);
+  h[24] = 1;
+  h[25] = 2;
+  const char* sys = "ICP Registration";
+  std::memcpy(h + 26, sys, std::strlen(sys));
+  const char* sw = "Custom ICP";
+  std::memcpy(h + 58, sw, std::strlen(sw));
+  wr<uint16_t>(h + 90, 307);
+  wr<uint16_t>(h + 92, 2025);
+  wr<uint16_t>(h + 94, 227);
+  wr<uint32_t>(h + 96, 227);
+  wr<uint32_t>(h + 100, 0);
+  h[104] = 0;
+  wr<uint16_t>(h + 105, 20);
+  wr<uint32_t>(h + 107, n);
+  for (int a = 0; a < 3; a++) {
+    wr<double>(h + 131 + 8 * a, scale[a]);
+    wr<double>(h + 155 + 8 * a, offset[a]);
+    wr<double>(h + 179 + 16 * a, mx[a]);
+    wr<double>(h + 187 + 16 * a, mn[a]);
+  }
+}
+
+}  // namespace icp
 
 extern "C" {
 
@@ -100,21 +151,7 @@ int icp_las_write_core_bounds(const char* path, const double* xyz, int64_t n, co
   std::ofstream f(path, std::ios::binary);
   if (!f.is_open()) return -1;
   char h[227];
-  std::memset(h, 0, sizeof(h));
-  std::memcpy(h, "LASF", 4);
-  h[24] = 1;
-  h[25] = 2;
-  wr<uint16_t>(h + 94, 227);
-  wr<uint32_t>(h + 96, 227);
-  h[104] = 0;
-  wr<uint16_t>(h + 105, 20);
-  wr<uint32_t>(h + 107, (uint32_t)n);
-  for (int a = 0; a < 3; a++) {
-    wr<double>(h + 131 + 8 * a, 0.001);
-    wr<double>(h + 155 + 8 * a, mn[a]);
-    wr<double>(h + 179 + 16 * a, mx[a]);
-    wr<double>(h + 187 + 16 * a, mn[a]);
-  }
+  icp::las_header_core(h, (uint32_t)n, mn, mx);
   f.write(h, 227);
   std::vector<char> rec((size_t)n * 20, 0);
   for (int64_t i = 0; i < n; i++)
@@ -145,23 +182,6 @@ int icp_las_write_cli(const char* path, const double* xyz, int64_t n, const doub
   if (n <= 0) return -2;  // the reference reads points[0] unconditionally (:762)
   std::ofstream f(path, std::ios::binary);
   if (!f.is_open()) return -1;
-  char h[227];
-  std::memset(h, 0, sizeof(h));
-  std::memcpy(h, "LASF", 4);
-  h[24] = 1;
-  h[25] = 2;
-  const char* sys = "ICP Registration";
-  std::memcpy(h + 26, sys, std::strlen(sys));
-  const char* sw = "Custom ICP";
-  std::memcpy(h + 58, sw, std::strlen(sw));
-  wr<uint16_t>(h + 90, 307);
-  wr<uint16_t>(h + 92, 2025);
-  wr<uint16_t>(h + 94, 227);
-  wr<uint32_t>(h + 96, 227);
-  wr<uint32_t>(h + 100, 0);
-  h[104] = 0;
-  wr<uint16_t>(h + 105, 20);
-  wr<uint32_t>(h + 107, (uint32_t)n);
   double mn[3], mx[3];
   for (int a = 0; a < 3; a++) mn[a] = mx[a] = xyz[a];
   for (int64_t i = 0; i < n; i++)
@@ -170,12 +190,8 @@ int icp_las_write_cli(const char* path, const double* xyz, int64_t n, const doub
       if (v < mn[a]) mn[a] = v;
       if (v > mx[a]) mx[a] = v;
     }
-  for (int a = 0; a < 3; a++) {
-    wr<double>(h + 131 + 8 * a, scale[a]);
-    wr<double>(h + 155 + 8 * a, offset[a]);
-    wr<double>(h + 179 + 16 * a, mx[a]);
-    wr<double>(h + 187 + 16 * a, mn[a]);
-  }
+  char h[227];
+  icp::las_header_cli(h, (uint32_t)n, scale, offset, mn, mx);
   f.write(h, 227);
   std::vector<char> rec((size_t)n * 20, 0);
   for (int64_t i = 0; i < n; i++)
