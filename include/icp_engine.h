@@ -122,6 +122,23 @@ int icp_session_step_n(icp_session* s, int32_t k, int32_t* steps_done, int32_t* 
 /* icp_session_step_n that also stores each step's host wall time (ms, steady clock; the step
  * returns when its record is on the host, so this is the whole iteration). step_ms[k]. */
 int icp_session_step_n_timed(icp_session* s, int32_t k, int32_t* steps_done, int32_t* done, double* step_ms);
+/* The error metric of a session's steps. ICP_METRIC_POINT (the default) is the reference's
+ * point-to-point loop. ICP_METRIC_PLANE takes the same decisions from the same statistics
+ * (convergence, divergence and too-few on the point-to-point RMSE, before the fit), but its
+ * increment is the point-to-plane step: icp_hip_plane_sums about the iterate's centroid_src, then
+ * icp_plane_solve; an iteration whose solve refuses takes the SVD step instead. A plane session
+ * steps on the host (never the device-resident loop) and needs normals on the context
+ * (ICP_HIP_ENOTREADY without them; ICP_HIP_EINVAL on a multi-device context or one with a
+ * communicator). Call it before the first step: later it returns ICP_HIP_EINVAL. */
+#define ICP_METRIC_POINT 0
+#define ICP_METRIC_PLANE 1
+int icp_session_set_metric(icp_session* s, int32_t metric);
+/* The last step of a plane session: its sums (zeros when the step computed none: a stop, or a
+ * point session) and whether the plane solve gave the increment. Either output may be null. */
+int icp_session_last_plane(const icp_session* s, icp_plane_sums* out, int32_t* used_plane);
+/* icp_engine_run with a metric. */
+int icp_engine_run_metric(icp_hip_ctx* ctx, const icp_params* p, int32_t metric, icp_result* res,
+                          icp_iteration_record* history, int32_t history_cap, const icp_engine_hooks* hooks);
 int icp_session_finish(icp_session* s, icp_result* res);
 /* Current cumulative transform (row-major 4x4). */
 void icp_session_transform(const icp_session* s, double T_cum[16]);

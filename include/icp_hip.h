@@ -431,6 +431,64 @@ int icp_hip_get_correspondences_device(icp_hip_ctx* ctx, int32_t* d_idx_out, dou
 /* icp_hip_nn with queries and answers in device buffers (either output may be null). */
 int icp_hip_nn_device(icp_hip_ctx* ctx, const double* d_q_xyz, int64_t n, int32_t* d_idx_out, double* d_dist_out);
 
+/* --- k nearest neighbours, target normals and the point-to-plane sums. Beside the
+ * reference's loop: nothing here changes what the calls above compute. */
+
+/* The k nearest target points of each query (AoS xyz), through the resident octree: the k points
+ * smallest under the order (fl(d2), original index), fl(d2) = dx*dx + dy*dy + dz*dz evaluated left
+ * to right in fp64 without FMA, ascending. The tie rule is the index, not the 1-NN's visit order, so
+ * that the set does not depend on the traversal. Outputs are n x k: original target indices and
+ * fl(d2); either may be null. A query with a non-finite coordinate gets indices -1 and NaN.
+ * ICP_HIP_EINVAL for k < 1, k > ICP_HIP_KNN_MAX or k > the target size; ICP_HIP_ENOTREADY without a
+ * target. The _device variant follows the contract of the *_device calls above. A multi-device
+ * context runs it on its first member (the octree is replicated). */
+#define ICP_HIP_KNN_MAX 32
+int icp_hip_knn(icp_hip_ctx* ctx, const double* q_xyz, int64_t n, int k, int32_t* idx_out, double* d2_out);
+int icp_hip_knn_device(icp_hip_ctx* ctx, const double* d_q_xyz, int64_t n, int k, int32_t* d_idx_out,
+                       double* d_d2_out);
+
+/* One unit normal per target point from its k nearest target points (k in [3, ICP_HIP_KNN_MAX], the
+ * point itself included unless k or more copies of it have lower indices): m = (sum p_i) / k in
+ * neighbour order, C = sum (p_i - m)(p_i - m)^T in fp64, the normal the unit eigenvector of C's
+ * smallest eigenvalue. Sign: with a viewpoint v (double[3]) n.(v - p) >= 0; with null the component of
+ * largest magnitude is positive (ties: the lowest axis). A neighbourhood whose C has fewer than two
+ * positive eigenvalues (copies, collinear points) gets the normal (0, 0, 0). icp_hip_set_target drops
+ * the normals. */
+int icp_hip_estimate_target_normals(icp_hip_ctx* ctx, int k, const double* viewpoint);
+/* Normals the caller already has, in the caller's target order (n_tgt x 3). Every row is of unit
+ * length (|n.n - 1| <= 1e-12) or zero, else ICP_HIP_EINVAL and the context's normals stay as they were. */
+int icp_hip_set_target_normals(icp_hip_ctx* ctx, const double* n_xyz);
+int icp_hip_set_target_normals_device(icp_hip_ctx* ctx, const double* d_n_xyz);
+/* The context's normals in the caller's target order; ICP_HIP_ENOTREADY when there are none. */
+int icp_hip_get_target_normals(icp_hip_ctx* ctx, double* n_xyz_out);
+int icp_hip_get_target_normals_device(icp_hip_ctx* ctx, double* d_n_xyz_out);
+
+/* The point-to-plane normal equations of the last iterate's valid pairs (d <= threshold, as the
+ * cull) whose target normal is not zero: with a' = a - origin, r = n.(a - b), J = (a' x n, n):
+ * A = sum J J^T (6 x 6, symmetric, row-major), g = sum J r, sum_r2 = sum r^2, n the pairs summed and
+ * n_skipped the valid pairs left out for a zero normal. */
+typedef struct icp_plane_sums {
+  double A[36];
+  double g[6];
+  double sum_r2;
+  int64_t n;
+  int64_t n_skipped;
+  double origin[3];
+} icp_plane_sums;
+
+/* The sums, after icp_hip_iterate on a context with normals. Reads what the iterate left resident
+ * (moved source, matches, residuals, threshold) and writes none of it. Deterministic: fixed parts of
+ * 4096 queries, a fixed tree inside a part, the parts added in index order.
+ * ICP_HIP_ENOTREADY before an iterate or without normals; ICP_HIP_EINVAL on a multi-device context and
+ * on one with a communicator (the sums are not exchanged between ranks). */
+int icp_hip_plane_sums(icp_hip_ctx* ctx, const double origin[3], icp_plane_sums* out);
+
+/* The point-to-plane step from the sums (host, no GPU): A x = -g, x = (w, t'), by Cholesky of the
+ * matrix scaled to a unit diagonal; R the Rodrigues rotation of w; T (row-major 4x4) maps
+ * x -> R (x - c) + c + t', c = sums->origin. *ok = 0 and T untouched when sums->n < 6, a diagonal
+ * entry of A is not positive, or a pivot of the scaled matrix is at most 2^-26. */
+void icp_plane_solve(const icp_plane_sums* sums, double T[16], int32_t* ok);
+
 /* Work of the reference DFS for the resident source (node entries and leaf points compared,
  * both as the reference visits them) — the V and P of the roofline byte model. */
 int icp_hip_traversal_counts(icp_hip_ctx* ctx, double* mean_node_entries, double* mean_leaf_points);

@@ -27,6 +27,8 @@ XPORT_CALLBACK = 3
 OK, EINVAL, ENOMEM, EDEVICE, ERCCL, ENOTREADY, EEXCHANGE = 0, -1, -2, -3, -4, -5, -6
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2  # icp_hip_dev_copy directions
 DBG_SLOTS = 40
+METRIC_POINT, METRIC_PLANE = 0, 1  # icp_engine.h ICP_METRIC_*
+KNN_MAX = 32
 # icp_hip.h ICP_DBG_* slot names
 DBG_NAMES = {0: "waves", 1: "overflow_waves", 2: "not_joined", 3: "not_covered", 4: "scanned_points",
              8: "fp64_scan_waves", 9: "staged_points", 10: "scan_pairs", 11: "scan_rounds",
@@ -150,6 +152,14 @@ class SceneSpec(C.Structure):
     ]
 
 
+class PlaneSums(C.Structure):
+    """icp_plane_sums (include/icp_hip.h): the point-to-plane normal equations of an iterate."""
+    _fields_ = [
+        ("A", C.c_double * 36), ("g", C.c_double * 6), ("sum_r2", C.c_double), ("n", C.c_int64),
+        ("n_skipped", C.c_int64), ("origin", C.c_double * 3),
+    ]
+
+
 _EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double))
 
 # (name, restype, argtypes) for every exported symbol; also the list the ABI test checks
@@ -181,6 +191,15 @@ SIGNATURES = {
     "icp_hip_get_source_device": (C.c_int, [_P, _P]),
     "icp_hip_get_correspondences_device": (C.c_int, [_P, _P, _P]),
     "icp_hip_nn_device": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "icp_hip_knn": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P]),
+    "icp_hip_knn_device": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P]),
+    "icp_hip_estimate_target_normals": (C.c_int, [_P, C.c_int, _P]),
+    "icp_hip_set_target_normals": (C.c_int, [_P, _P]),
+    "icp_hip_set_target_normals_device": (C.c_int, [_P, _P]),
+    "icp_hip_get_target_normals": (C.c_int, [_P, _P]),
+    "icp_hip_get_target_normals_device": (C.c_int, [_P, _P]),
+    "icp_hip_plane_sums": (C.c_int, [_P, _P, C.POINTER(PlaneSums)]),
+    "icp_plane_solve": (None, [C.POINTER(PlaneSums), _P, _I32]),
     "icp_hip_traversal_counts": (C.c_int, [_P, _D, _D]),
     "icp_hip_target_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I32, _I32]),
     "icp_hip_last_timing": (C.c_int, [_P, _D, _D]),
@@ -211,6 +230,10 @@ SIGNATURES = {
     "icp_session_step_n": (C.c_int, [_P, C.c_int32, _I32, _I32]),
     "icp_session_step_n_timed": (C.c_int, [_P, C.c_int32, _I32, _I32, _P]),
     "icp_session_finish": (C.c_int, [_P, C.POINTER(Result)]),
+    "icp_session_set_metric": (C.c_int, [_P, C.c_int32]),
+    "icp_session_last_plane": (C.c_int, [_P, C.POINTER(PlaneSums), _I32]),
+    "icp_engine_run_metric": (C.c_int, [_P, C.POINTER(Params), C.c_int32, C.POINTER(Result),
+                                        C.POINTER(IterationRecord), C.c_int32, C.POINTER(Hooks)]),
     "icp_session_transform": (None, [_P, _P]),
     "icp_session_destroy": (None, [_P]),
     "icp_cli_icp": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_double, _P, _P, _P, C.c_int32,
@@ -470,6 +493,49 @@ class Context:
     def nn_device(self, d_q, n: int, d_idx_out=None, d_dist_out=None):
         _check(lib().icp_hip_nn_device(self._h, _dptr(d_q), n, _dptr(d_idx_out), _dptr(d_dist_out)))
 
+    # --- k nearest neighbours, target normals, the point-to-plane sums (include/icp_hip.h)
+    def knn(self, q, k: int):
+        """The k nearest target points of each query under (fl(d2), original index), ascending:
+        (indices (n, k) int32, fl(d2) (n, k) float64)."""
+        q = _aos(q)
+        idx = np.empty((q.shape[0], max(k, 0)), np.int32)
+        d2 = np.empty((q.shape[0], max(k, 0)), np.float64)
+        _check(lib().icp_hip_knn(self._h, _ptr(q), q.shape[0], k, _ptr(idx), _ptr(d2)))
+        return idx, d2
+
+    def knn_device(self, d_q, n: int, k: int, d_idx_out=None, d_d2_out=None):
+        _check(lib().icp_hip_knn_device(self._h, _dptr(d_q), n, k, _dptr(d_idx_out), _dptr(d_d2_out)))
+
+    def estimate_target_normals(self, k: int = 16, viewpoint=None):
+        v = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float64).reshape(3)
+        _check(lib().icp_hip_estimate_target_normals(self._h, k, _ptr(v)))
+
+    def set_target_normals(self, n_xyz):
+        """Normals in the caller's target order: a DeviceBuffer / device address, or an (n, 3) array."""
+        if isinstance(n_xyz, (DeviceBuffer, int)):
+            _check(lib().icp_hip_set_target_normals_device(self._h, _dptr(n_xyz)))
+            return
+        n_xyz = _aos(n_xyz)
+        if n_xyz.shape[0] != self._n_tgt:
+            raise ValueError("one normal per target point")
+        _check(lib().icp_hip_set_target_normals(self._h, _ptr(n_xyz)))
+
+    def get_target_normals(self, d_out=None):
+        """The target's normals, caller's order: an (n, 3) array, or written to the device buffer d_out."""
+        if d_out is not None:
+            _check(lib().icp_hip_get_target_normals_device(self._h, _dptr(d_out)))
+            return d_out
+        out = np.empty((self._n_tgt, 3), np.float64)
+        _check(lib().icp_hip_get_target_normals(self._h, _ptr(out)))
+        return out
+
+    def plane_sums(self, origin=(0.0, 0.0, 0.0)) -> PlaneSums:
+        """The point-to-plane sums of the last iterate's valid pairs about `origin`."""
+        o = np.ascontiguousarray(origin, np.float64).reshape(3)
+        out = PlaneSums()
+        _check(lib().icp_hip_plane_sums(self._h, _ptr(o), C.byref(out)))
+        return out
+
     # --- LAS files to and from device-resident clouds (include/icp_las.h)
     def read_las_device(self, path, rules=1, max_points=0, stride=1):
         """Decode a LAS file into a new DeviceBuffer. Returns (buffer, n points, header)."""
@@ -612,13 +678,17 @@ class Context:
         _check(lib().icp_hip_debug_counters(self._h, _ptr(out)))
         return {name: int(out[k]) for k, name in DBG_NAMES.items()}
 
-    def session(self, params: Params) -> "Session":
-        return Session(self, params)
+    def session(self, params: Params, metric: int | None = None) -> "Session":
+        """metric None: the session's default (ICP_METRIC_POINT), no icp_session_set_metric call."""
+        return Session(self, params, metric=metric)
 
-    def run(self, params: Params, history_cap: int = 1024):
+    def run(self, params: Params, history_cap: int = 1024, metric: int = METRIC_POINT):
         res = Result()
         hist = (IterationRecord * max(1, history_cap))()
-        rc = lib().icp_engine_run(self._h, C.byref(params), C.byref(res), hist, history_cap, None)
+        if metric == METRIC_POINT:
+            rc = lib().icp_engine_run(self._h, C.byref(params), C.byref(res), hist, history_cap, None)
+        else:
+            rc = lib().icp_engine_run_metric(self._h, C.byref(params), metric, C.byref(res), hist, history_cap, None)
         return rc, res, [hist[k] for k in range(res.n_history)]
 
 
@@ -678,11 +748,23 @@ class DeviceBuffer:
 class Session:
     """Steppable ICP loop on a context (icp_session_*): one step = one reference loop body."""
 
-    def __init__(self, ctx: Context, params: Params):
+    def __init__(self, ctx: Context, params: Params, metric: int | None = None):
         self._ctx = ctx  # keep alive
         self._h = C.c_void_p()
         _check(lib().icp_session_create(ctx.handle, C.byref(params), None, C.byref(self._h)))
         self.done = False
+        if metric is not None:
+            self.set_metric(metric)
+
+    def set_metric(self, metric: int):
+        """ICP_METRIC_POINT / ICP_METRIC_PLANE, before the first step (icp_session_set_metric)."""
+        _check(lib().icp_session_set_metric(self._h, metric))
+
+    def last_plane(self):
+        """(sums, used_plane) of the last step of a plane session (icp_session_last_plane)."""
+        out, used = PlaneSums(), C.c_int32(0)
+        _check(lib().icp_session_last_plane(self._h, C.byref(out), C.byref(used)))
+        return out, used.value
 
     def step(self):
         rec = IterationRecord()
@@ -866,6 +948,15 @@ def jacobi_svd3(H):
     U, S, V = np.empty(9), np.empty(3), np.empty(9)
     lib().icp_jacobi_svd3(_ptr(H), _ptr(U), _ptr(S), _ptr(V))
     return U.reshape(3, 3), S, V.reshape(3, 3)
+
+
+def plane_solve(sums: PlaneSums):
+    """The point-to-plane step of the sums (icp_plane_solve): (T (4, 4), ok). ok = 0: the solve
+    refused and T is returned as the NaN-filled array it was handed."""
+    T = np.full(16, np.nan)
+    ok = C.c_int32(0)
+    lib().icp_plane_solve(C.byref(sums), _ptr(T), C.byref(ok))
+    return T.reshape(4, 4), ok.value
 
 
 def best_fit_transform(a, b):

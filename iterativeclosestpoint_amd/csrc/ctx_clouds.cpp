@@ -41,6 +41,7 @@ static hipError_t reset_band(icp_hip_ctx* c) {
 
 void free_target(icp_hip_ctx* c) {
   drain_prewalk(c);
+  plane_free_target(c);  // normals name the points of this tree
   dfree(c->nodes);
   dfree(c->tbox);
   dfree(c->pts);

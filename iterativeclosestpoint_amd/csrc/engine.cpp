@@ -100,6 +100,9 @@ struct icp_session {
   icp::SessionParams sp;
   int rc_final = ICP_HIP_OK;
   char message[160] = {0};
+  int32_t metric = ICP_METRIC_POINT;
+  icp_plane_sums plane{};  // the last step's sums (plane metric)
+  int32_t used_plane = 0;  // the last step's increment came from the plane solve
 };
 
 extern "C" {
@@ -124,6 +127,26 @@ int icp_session_create(icp_hip_ctx* ctx, const icp_params* p, const icp_engine_h
 }
 
 void icp_session_destroy(icp_session* s) { delete s; }
+
+int icp_session_set_metric(icp_session* s, int32_t metric) {
+  if (!s || (metric != ICP_METRIC_POINT && metric != ICP_METRIC_PLANE)) return fail(ICP_HIP_EINVAL, "set_metric: bad arguments");
+  if (s->core.iter != 0) return fail(ICP_HIP_EINVAL, "set_metric: the session has already stepped");
+  if (metric == ICP_METRIC_PLANE) {
+    const icp_hip_ctx* c = s->ctx;
+    if (c->group) return fail(ICP_HIP_EINVAL, "set_metric: the plane metric does not run on a multi-device context");
+    if (c->comm || c->xfn) return fail(ICP_HIP_EINVAL, "set_metric: the plane metric does not run with a communicator");
+    if (!c->normals) return fail(ICP_HIP_ENOTREADY, "set_metric: the target has no normals");
+  }
+  s->metric = metric;
+  return ICP_HIP_OK;
+}
+
+int icp_session_last_plane(const icp_session* s, icp_plane_sums* out, int32_t* used_plane) {
+  if (!s) return ICP_HIP_EINVAL;
+  if (out) *out = s->plane;
+  if (used_plane) *used_plane = s->used_plane;
+  return ICP_HIP_OK;
+}
 
 void icp_session_transform(const icp_session* s, double T_cum[16]) { std::memcpy(T_cum, s->core.Tc, sizeof(s->core.Tc)); }
 
@@ -222,8 +245,32 @@ int icp_session_step(icp_session* s, icp_iteration_record* rec, int32_t* produce
       return rc;
     }
     s->core.pending = 0;
+    double Tc_before[16];
+    std::memcpy(Tc_before, s->core.Tc, sizeof(Tc_before));
     const int32_t outcome = icp::session_core_step(s->core, s->sp, st.rmse, st.valid, st.centroid_src,
                                                    st.centroid_tgt, st.H);
+    if (s->metric == ICP_METRIC_PLANE) {
+      // the decisions above are the point-to-point loop's; a step that fits takes its increment
+      // from the plane sums about the valid pairs' source centroid, unless the solve refuses
+      std::memset(&s->plane, 0, sizeof(s->plane));
+      s->used_plane = 0;
+      if (outcome == icp::kStepTransform) {
+        const int prc = icp_hip_plane_sums(s->ctx, st.centroid_src, &s->plane);
+        if (prc != ICP_HIP_OK) {
+          s->rc_final = prc;
+          std::snprintf(s->message, sizeof(s->message), "%s", icp_hip_last_error());
+          s->core.done = 1;
+          if (done) *done = 1;
+          return prc;
+        }
+        double Tp[16];
+        icp_plane_solve(&s->plane, Tp, &s->used_plane);
+        if (s->used_plane) {
+          std::memcpy(s->core.T, Tp, sizeof(Tp));
+          icp::svd::mat4_mul(Tp, Tc_before, s->core.Tc);
+        }
+      }
+    }
     emit_iteration(s, iter, outcome, st, s->core.T, s->core.Tc, rec, produced);
   }
   if (done) *done = s->core.done ? 1 : 0;
@@ -244,7 +291,8 @@ static int session_run(icp_session* s, int32_t k, int32_t* steps_done, int32_t* 
   // (icpengine.cpp:160-164; a flag raised from a progress hook stops the next iteration): such a
   // session steps on the host.
   const bool per_iteration_stop = s->h && s->h->stop_flag;
-  if (icp_hip_loop_eligible(s->ctx) && !per_iteration_stop) {
+  // a plane session steps on the host too (its increment is not the device step's)
+  if (icp_hip_loop_eligible(s->ctx) && !per_iteration_stop && s->metric == ICP_METRIC_POINT) {
     std::vector<icp::LoopRec> recs((size_t)icp_hip_ctx::kLoopRing);
     std::vector<double> ms((size_t)icp_hip_ctx::kLoopRing);
     while (n < k && !s->core.done && rc == ICP_HIP_OK) {
@@ -355,10 +403,21 @@ int icp_session_finish(icp_session* s, icp_result* res) {
 
 int icp_engine_run(icp_hip_ctx* ctx, const icp_params* p, icp_result* res, icp_iteration_record* hist,
                    int32_t cap, const icp_engine_hooks* hooks) {
+  return icp_engine_run_metric(ctx, p, ICP_METRIC_POINT, res, hist, cap, hooks);
+}
+
+int icp_engine_run_metric(icp_hip_ctx* ctx, const icp_params* p, int32_t metric, icp_result* res,
+                          icp_iteration_record* hist, int32_t cap, const icp_engine_hooks* hooks) {
   if (!ctx || !p || !res) return ICP_HIP_EINVAL;
   icp_session* s = nullptr;
   int rc = icp_session_create(ctx, p, hooks, &s);
   if (rc != ICP_HIP_OK) return rc;
+  if (metric != ICP_METRIC_POINT && (rc = icp_session_set_metric(s, metric)) != ICP_HIP_OK) {
+    std::memset(res, 0, sizeof(*res));
+    set_msg(res, icp_hip_last_error());
+    icp_session_destroy(s);
+    return rc;
+  }
   int32_t n = 0, done = 0, steps = 0;
   // the device loop in batches of kEngineBatch (iterations enqueued past convergence return at
   // once), else host steps

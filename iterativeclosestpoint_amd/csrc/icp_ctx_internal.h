@@ -121,6 +121,12 @@ struct icp_hip_ctx {
   int las_device_path = -1;      // icp_hip_last_las_path: 1 kernels, 0 host reader / writer, -1 none yet
   size_t las_chunk_bytes = 8u << 20;  // icp_hip_set_las_chunk_bytes
 
+  // --- point-to-plane (ctx_plane.cpp): the target's normals (leaf order, 3 x fp64; null: none) and
+  // the part sums of icp_hip_plane_sums (made at first use, released with the target)
+  double* normals = nullptr;
+  double* plane_parts = nullptr;  // plane_cap parts + the merged sums (kPlaneSums doubles each)
+  int64_t plane_cap = 0;
+
   // --- multi-device context (icp_hip_create_multi): the member contexts and their driver threads
   // (icp_group.cpp); the single-device fields above are then unused
   struct DeviceGroup* group = nullptr;
@@ -157,6 +163,9 @@ int prewalk_join(icp_hip_ctx* c, hipStream_t s);
 // overwrites the transform (LoopDev::core.T) that the prewalk's lead reads while it would run.
 bool prewalk_arm(icp_hip_ctx* c, icp::NNLaunch& a, const icp::LoopDev* loop, bool apply);
 int prewalk_launch(icp_hip_ctx* c, const icp::NNLaunch& a);  // after launch_nn of an armed iterate
+
+// --- ctx_plane.cpp
+void plane_free_target(icp_hip_ctx* c);  // free_target's part: the normals and the plane sums' buffers
 
 // --- ctx_las.cpp
 void las_destroy(icp_hip_ctx* c);  // the staging buffers released (icp_hip_destroy)

@@ -6,6 +6,11 @@
 //   icp_registration [--source Scan_096_origin.las] [--target Scannew_099.las]
 //                    [--sample-rate 50] [--max-iters 20] [--tolerance 1e-2]
 //                    [--outdir .] [--device 0 | --devices 0,1,...] [--device-io] [--pause]
+//                    [--metric point|plane] [--normals-k 16]
+//
+// --metric plane registers with the point-to-plane step (icp_engine_run_metric, ICP_METRIC_PLANE):
+// the target's normals are estimated from --normals-k neighbours once the target is set; the CLI's
+// rules, decisions and files otherwise. One GPU only. Without the flag every output is unchanged.
 //
 // --devices runs one registration over several GPUs of this process (icp_cli_icp_devices: the
 // source sharded over them, the octree replicated, RCCL all-gathers per iteration).
@@ -40,12 +45,15 @@ struct Args {
   std::vector<int> devices{0};
   bool device_io = false;
   bool pause = false;
+  int metric = ICP_METRIC_POINT;
+  int normals_k = 16;
 };
 
 [[noreturn]] void usage(const char* prog, int code) {
   std::fprintf(code ? stderr : stdout,
                "usage: %s [--source F] [--target F] [--sample-rate N] [--max-iters N] [--tolerance X]\n"
-               "          [--outdir D] [--device N | --devices N,M,...] [--device-io] [--pause]\n",
+               "          [--outdir D] [--device N | --devices N,M,...] [--device-io] [--pause]\n"
+               "          [--metric point|plane] [--normals-k N]\n",
                prog);
   std::exit(code);
 }
@@ -81,6 +89,13 @@ Args parse(int argc, char** argv) {
       }
     }
     else if (k == "--device-io") a.device_io = true;
+    else if (k == "--metric") {
+      const std::string m = val();
+      if (m == "point") a.metric = ICP_METRIC_POINT;
+      else if (m == "plane") a.metric = ICP_METRIC_PLANE;
+      else usage(argv[0], 2);
+    }
+    else if (k == "--normals-k") a.normals_k = (int)std::strtol(val(), nullptr, 10);
     else if (k == "--pause") a.pause = true;
     else if (k == "-h" || k == "--help") usage(argv[0], 0);
     else usage(argv[0], 2);
@@ -92,6 +107,14 @@ Args parse(int argc, char** argv) {
   if (a.device_io && a.devices.size() > 1) {
     std::fprintf(stderr, "--device-io runs on one GPU (clouds resident across a device group: not supported)\n");
     usage(argv[0], 2);
+  }
+  if (a.metric == ICP_METRIC_PLANE && a.devices.size() > 1) {
+    std::fprintf(stderr, "--metric plane runs on one GPU (the plane sums are not exchanged between devices)\n");
+    usage(argv[0], 2);
+  }
+  if (a.metric == ICP_METRIC_PLANE && (a.normals_k < 3 || a.normals_k > ICP_HIP_KNN_MAX)) {
+    std::fprintf(stderr, "--normals-k must be in [3, %d]\n", ICP_HIP_KNN_MAX);
+    std::exit(2);
   }
   return a;
 }
@@ -178,7 +201,11 @@ int run_device_io(const Args& a) {
   icp_result res;
   if (icp_hip_set_target_device(ctx, static_cast<double*>(d_tgt), nt, 10, 20, ICP_RULES_CLI) != ICP_HIP_OK)
     return bail("registration failed");
-  const int rc = icp_engine_run(ctx, &p, &res, hist.data(), cap, nullptr);
+  if (a.metric == ICP_METRIC_PLANE) {
+    std::cout << "metric: point-to-plane, normals from " << a.normals_k << " neighbours" << std::endl;
+    if (icp_hip_estimate_target_normals(ctx, a.normals_k, nullptr) != ICP_HIP_OK) return bail("cannot estimate the target normals");
+  }
+  const int rc = icp_engine_run_metric(ctx, &p, a.metric, &res, hist.data(), cap, nullptr);
   if (rc != ICP_HIP_OK) {
     std::cerr << "ICP failed (" << rc << ")";
     return bail("registration failed");
@@ -204,6 +231,38 @@ int run_device_io(const Args& a) {
   std::cout << "\ndone: registered_source.las, registered_target.las, icp_transformation.txt" << std::endl;
   if (a.pause) std::cin.get();
   return 0;
+}
+
+// ICP() with the point-to-plane step on host clouds: icp_cli_icp_devices' steps on one context, with
+// the normals estimated once the target is set. src is moved in place.
+int cli_icp_plane(const Args& a, double* src, int64_t ns, const double* tgt, int64_t nt, double R[9], double t[3],
+                  double* transforms, int32_t cap, int32_t* n_tr) {
+  icp_params p;
+  icp_params_default(&p);
+  p.max_iterations = a.max_iters;
+  p.tolerance = a.tolerance;
+  p.rules = ICP_RULES_CLI;
+  std::vector<icp_iteration_record> hist((size_t)cap);
+  icp_result res;
+  icp_hip_ctx* ctx = nullptr;
+  int rc = icp_hip_create(&ctx, a.devices[0]);
+  if (rc == ICP_HIP_OK) rc = icp_hip_set_target(ctx, tgt, nt, 10, 20, ICP_RULES_CLI);
+  if (rc == ICP_HIP_OK) rc = icp_hip_estimate_target_normals(ctx, a.normals_k, nullptr);
+  if (rc == ICP_HIP_OK) rc = icp_hip_set_source(ctx, src, ns);
+  if (rc == ICP_HIP_OK) rc = icp_engine_run_metric(ctx, &p, ICP_METRIC_PLANE, &res, hist.data(), cap, nullptr);
+  if (rc == ICP_HIP_OK) rc = icp_hip_get_source(ctx, src);
+  icp_hip_destroy(ctx);
+  if (rc != ICP_HIP_OK) return rc;
+  std::memcpy(R, res.final_R, sizeof(res.final_R));
+  std::memcpy(t, res.final_t, sizeof(res.final_t));
+  int32_t m = 0;
+  for (int32_t k = 0; k < res.n_history; k++) {
+    if (!hist[k].has_transform) continue;
+    if (m < cap) std::memcpy(transforms + 16 * (size_t)m, hist[k].transform, 16 * sizeof(double));
+    m++;
+  }
+  *n_tr = m;
+  return ICP_HIP_OK;
 }
 
 }  // namespace
@@ -242,8 +301,12 @@ int main(int argc, char** argv) {
   std::vector<double> transforms((size_t)cap * 16);
   int32_t n_tr = 0;
   if (a.devices.size() > 1) std::cout << "devices: " << a.devices.size() << " GPUs" << std::endl;
-  const int rc = icp_cli_icp_devices(ss.data(), ns, ts.data(), nt, a.max_iters, a.tolerance, R, t, transforms.data(),
-                                     cap, &n_tr, (int)a.devices.size(), a.devices.data());
+  if (a.metric == ICP_METRIC_PLANE)
+    std::cout << "metric: point-to-plane, normals from " << a.normals_k << " neighbours" << std::endl;
+  const int rc = a.metric == ICP_METRIC_PLANE
+                     ? cli_icp_plane(a, ss.data(), ns, ts.data(), nt, R, t, transforms.data(), cap, &n_tr)
+                     : icp_cli_icp_devices(ss.data(), ns, ts.data(), nt, a.max_iters, a.tolerance, R, t, transforms.data(),
+                                           cap, &n_tr, (int)a.devices.size(), a.devices.data());
   if (rc != 0) {
     std::cerr << "ICP failed (" << rc << "): " << icp_hip_last_error() << std::endl;
     return fail(a, "registration failed");

@@ -217,6 +217,43 @@ hipError_t launch_cull_tail(const CullLaunch& a, unsigned* ticket, const IterPub
 // Merge `nranks` gathered covariance moments in rank order, RMSE, publish.
 hipError_t launch_finalize_cov(const CovMoments* gathered, int nranks, IterDev* it, IterPublish pub, hipStream_t s);
 
+// --- knn_kernels.hip: k nearest neighbours through the octree, the target's normals from them.
+// Threads per block of the k-NN kernels: the DFS stack (levels x 8 B) and the k-entry list
+// (k x 12 B) of every thread in LDS, at most 64 KiB per block.
+int knn_block_threads(int levels, int k);
+// The k nearest target points of n queries (AoS) under (fl(d2), original index), ascending:
+// idx_out / d2_out are n x k (either may be null).
+hipError_t launch_knn(const NodeRec* nodes, const TgtPt* pts, int levels, const double* q_aos, int64_t n, int k,
+                      int32_t* idx_out, double* d2_out, hipStream_t s);
+// One normal per target point (leaf order, 3 x fp64) from its k nearest target points; view: the
+// viewpoint of the sign rule (has_view = 0: largest component positive).
+hipError_t launch_target_normals(const NodeRec* nodes, const TgtPt* pts, int levels, int64_t n, int k, int has_view,
+                                 const double view[3], double* normals, hipStream_t s);
+// Normals between the caller's target order (aos) and leaf order (leaf). to_leaf also counts in *bad
+// the rows that are neither of unit length nor zero.
+hipError_t launch_normals_to_leaf(const TgtPt* pts, const double* aos, double* leaf, int64_t n, unsigned* bad,
+                                  hipStream_t s);
+hipError_t launch_normals_from_leaf(const TgtPt* pts, const double* leaf, double* aos, int64_t n, hipStream_t s);
+
+// --- plane_kernels.hip: the point-to-plane sums of the last iterate's valid pairs.
+constexpr int kPlaneSums = 32;  // 21 of J J^T (upper triangle, row by row), 6 of J r, r^2, n, skipped, 2 pad
+struct PlaneLaunch {
+  const double* x;
+  const double* y;
+  const double* z;
+  const int32_t* pos;
+  const double* dist;
+  const TgtPt* pts;
+  const double* normals;  // leaf order
+  const IterDev* it;      // the threshold
+  double origin[3];
+  int64_t n;
+  double* parts;  // plane_num_parts(n) x kPlaneSums
+  double* out;    // kPlaneSums
+};
+int64_t plane_num_parts(int64_t n);
+hipError_t launch_plane_sums(const PlaneLaunch& a, hipStream_t s);
+
 hipError_t launch_apply(const double T[12], double* x, double* y, double* z, int64_t n, hipStream_t s);
 hipError_t launch_scatter_aos(const int32_t* perm, const double* x, const double* y, const double* z,
                               double* aos, int64_t n, hipStream_t s);
