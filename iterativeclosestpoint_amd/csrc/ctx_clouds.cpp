@@ -21,8 +21,7 @@ void free_source(icp_hip_ctx* c) {
   dfree(c->perm);
   dfree(c->pos);
   dfree(c->dist);
-  dfree(c->fb_list);
-  dfree(c->fb_u);
+  c->follow.release(false);
   dfree(c->wc_box);
   dfree(c->wc_ents);
   dfree(c->mparts);
@@ -358,8 +357,7 @@ static int set_source_core(icp_hip_ctx* c, const double* xyz, const double* d_in
   HIP_TRY(dalloc(&c->perm, n));
   HIP_TRY(dalloc(&c->pos, n));
   HIP_TRY(dalloc(&c->dist, n));
-  HIP_TRY(dalloc(&c->fb_list, 3 * (size_t)n + 64));  // exact, ball, (half, mask) pairs
-  HIP_TRY(dalloc(&c->fb_u, (size_t)n));
+  HIP_TRY(c->follow.alloc(n));
   if (c->cfg.candidate_cache && n > 0) {
     // the cache only saves walks: without memory for it every iterate walks (identical results)
     const size_t nw = (size_t)((n + 63) / 64);
@@ -529,14 +527,16 @@ static int nn_core(icp_hip_ctx* c, bool dev, const double* q, int64_t n, int32_t
   // of fewer than 2^29 queries, so larger sets go in slices (the answers are per query)
   constexpr int64_t kSlice = (int64_t)1 << 28;
   if (n > kSlice) {
-    unsigned int lists[3] = {0, 0, 0};
+    PublishedLists lists{0, 0, 0};
     for (int64_t off = 0; off < n; off += kSlice) {
       const int64_t m = n - off < kSlice ? n - off : kSlice;
       const int rc = nn_core(c, dev, q + 3 * off, m, idx_out ? idx_out + off : nullptr, dist_out ? dist_out + off : nullptr);
       if (rc != ICP_HIP_OK) return rc;
-      for (int k = 0; k < 3; k++) lists[k] += c->last_lists[k];
+      lists.exact += c->follow.last.exact;
+      lists.ball += c->follow.last.ball;
+      lists.lane += c->follow.last.lane;
     }
-    for (int k = 0; k < 3; k++) c->last_lists[k] = lists[k];
+    c->follow.last = lists;
     return ICP_HIP_OK;
   }
   HIP_TRY(hipSetDevice(c->device));
@@ -559,24 +559,16 @@ static int nn_core(icp_hip_ctx* c, bool dev, const double* q, int64_t n, int32_t
     a.n = n;
     int32_t* fbl = nullptr;
     double* fbu = nullptr;
-    if (e == hipSuccess) e = dalloc(&fbl, 3 * (size_t)n + 64);
+    if (e == hipSuccess) e = dalloc(&fbl, (size_t)follow_list_ints(n));
     if (e == hipSuccess) e = dalloc(&fbu, (size_t)n);
-    a.fb_list = fbl;
-    a.fb_list2 = fbl + n;
-    a.fb_list3 = c->cfg.overflow_halves ? fbl + 2 * n : nullptr;
-    a.fb_list4 = c->cfg.scan32 && c->cfg.wide_pass != 1 ? wide_list(fbl, n) : nullptr;
-    a.fb_u2 = fbu;
-    a.fb_count = c->fb_count;
-    unsigned int lists4[4] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemsetAsync(c->fb_count, 0, 8 * sizeof(unsigned int), c->stream);
-    c->lists_zero = false;
+    a.follow = carve_follow_lists(fbl, fbu, c->follow.counts, n, c->cfg.overflow_halves != 0,
+                                  c->cfg.scan32 && c->cfg.wide_pass != 1);
+    FollowCounts counts{};
+    if (e == hipSuccess) e = c->follow.begin_search(c->stream);
     if (e == hipSuccess) e = launch_nn(a, c->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(lists4, c->fb_count, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&counts, c->follow.counts, sizeof(FollowCounts), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    c->last_lists[0] = lists4[0] + lists4[3];  // exact: the wave search's list + the ball's DFS finishes
-    c->last_lists[1] = lists4[1];
-    c->last_lists[2] = lists4[2];
+    c->follow.last = published_lists(counts);
     dfree(fbl);
     dfree(fbu);
     if (dev) {

@@ -57,11 +57,6 @@ static int wait_device(icp_hip_ctx* c, Done done, Progress progress, const char*
   return ICP_HIP_OK;
 }
 
-// The wide pass's list: after the exact and ball lists (2 n ints) and the half list (<= 2 halves
-// of every wave, two ints each: <= n / 16 + 4 ints); <= 3 entries per wave (the wave and its two
-// halves), three ints each: inside the 3 n + 64 ints of fb_list.
-int32_t* wide_list(int32_t* fbl, int64_t n) { return fbl + 2 * n + n / 16 + 8; }
-
 // config.wide_pass: 0 a source's first iterate (descent guesses: loose boxes) and any iterate after
 // one with >= max(kWideAuto, waves / kWideAutoDiv) overflowing waves (surface data far from
 // convergence); below that the ball search takes their queries sooner than a second launch (the
@@ -76,7 +71,7 @@ static bool wide_pass_on(const icp_hip_ctx* c) {
   if (!c->cfg.scan32 || c->cfg.search != ICP_SEARCH_CERTIFIED || c->cfg.wide_pass == 1) return false;
   const double rel = (double)((c->n_src + 63) / 64) / kWideAutoDiv;
   const double thr = rel > kWideAuto ? rel : kWideAuto;
-  return c->cfg.wide_pass == 2 || !c->have_prev || c->last_wide >= thr;
+  return c->cfg.wide_pass == 2 || !c->have_prev || c->follow.last_wide >= thr;
 }
 
 // Step 1 of an iterate: the search's launch record over the resident source.
@@ -92,15 +87,11 @@ static NNLaunch search_launch(const icp_hip_ctx* c, const double* T_apply, bool 
   a.apply = apply ? 1 : 0;
   if (T_apply)
     for (int k = 0; k < 12; k++) a.T[k] = T_apply[k];
-  a.fb_list = c->fb_list;
-  a.fb_list2 = c->fb_list + c->n_src;
   // the half pass pays off where many waves overflow: the first iterate of a source (descent
   // guesses, loose boxes; ~16 % of the waves at 10M). Later iterates overflow in ~0.2 % of the
   // waves, whose queries the ball search finishes sooner than a second serial launch.
-  a.fb_list3 = (c->cfg.overflow_halves && !c->have_prev) ? c->fb_list + 2 * c->n_src : nullptr;  // <= n + 64 ints
-  a.fb_list4 = wide_pass_on(c) ? wide_list(c->fb_list, c->n_src) : nullptr;
-  a.fb_u2 = c->fb_u;
-  a.fb_count = c->fb_count;
+  a.follow = carve_follow_lists(c->follow.ints, c->follow.guesses, c->follow.counts, c->n_src,
+                                c->cfg.overflow_halves && !c->have_prev, wide_pass_on(c));
   a.have_prev = c->have_prev ? 1 : 0;
   a.wc_box = c->wc_box;
   a.wc_ents = c->wc_ents;
@@ -117,8 +108,7 @@ static NNLaunch search_launch(const icp_hip_ctx* c, const double* T_apply, bool 
 // Step 2: the list counts and the debug counters cleared; the search's timing events (on dispatch
 // packets) from ring slot `slot`, on every timing_stride-th iterate only.
 static int clear_and_time(icp_hip_ctx* c, NNLaunch& a, int64_t slot, hipStream_t s) {
-  if (!c->lists_zero) HIP_TRY(hipMemsetAsync(c->fb_count, 0, 8 * sizeof(unsigned int), s));
-  c->lists_zero = false;
+  HIP_TRY(c->follow.begin_search(s));
   if (c->dbg) HIP_TRY(hipMemsetAsync(c->dbg, 0, ICP_DBG_SLOTS * sizeof(unsigned long long), s));
   const bool timed = c->cfg.timing_stride > 0 && c->n_iterates % c->cfg.timing_stride == 0;
   c->timed[slot] = timed;
@@ -181,7 +171,7 @@ static int moments_step(icp_hip_ctx* c, int64_t slot, LoopDev* loop, bool multi,
 // loop, sequence number *seq) or steps the device session (device loop); the iterate-end event.
 static int cull_step(icp_hip_ctx* c, int64_t slot, LoopDev* loop, int loop_slot, bool multi, const CullLaunch& cl,
                      hipStream_t s, uint64_t* seq) {
-  IterPublish pub{nullptr, c->fb_count, 0.0, nullptr, nullptr};
+  IterPublish pub{nullptr, c->follow.counts, 0.0, nullptr, nullptr};
   if (loop) {
     pub.loop = loop;
     pub.rec = c->h_ring_dev + loop_slot;
@@ -237,6 +227,11 @@ static int enqueue_iterate(icp_hip_ctx* c, const double* T_apply, bool apply, in
   return ICP_HIP_OK;
 }
 
+// A record's three list sizes (IterDev::lists, LoopRec::lists) back as counts.
+static PublishedLists record_lists(const double lists[3]) {
+  return PublishedLists{(unsigned int)lists[0], (unsigned int)lists[1], (unsigned int)lists[2]};
+}
+
 // The caller's statistics from the published record of a host-driven iterate.
 static void stats_from_record(const icp_hip_ctx* c, const IterDev& h, icp_iter_stats* out) {
   out->n = (int64_t)h.m_global.n;
@@ -255,9 +250,9 @@ static void stats_from_record(const icp_hip_ctx* c, const IterDev& h, icp_iter_s
   }
   for (int k = 0; k < 9; k++) out->H[k] = h.c_global.c[k];
   const bool cert = c->cfg.search == ICP_SEARCH_CERTIFIED;
-  out->n_fallback = cert ? (int64_t)c->last_lists[0] : 0;
-  out->n_lane_search = cert ? (int64_t)c->last_lists[2] : 0;
-  out->n_ball_search = cert ? (int64_t)c->last_lists[1] : 0;
+  out->n_fallback = cert ? (int64_t)c->follow.last.exact : 0;
+  out->n_lane_search = cert ? (int64_t)c->follow.last.lane : 0;
+  out->n_ball_search = cert ? (int64_t)c->follow.last.ball : 0;
 }
 
 extern "C" int icp_hip_iterate(icp_hip_ctx* c, const double* T_apply, int iter, int rules, double sigma_multiplier,
@@ -279,16 +274,14 @@ extern "C" int icp_hip_iterate(icp_hip_ctx* c, const double* T_apply, int iter, 
     const double want = (double)seq;
     uint64_t want_bits;
     std::memcpy(&want_bits, &want, sizeof(want));
-    const uint64_t* word = reinterpret_cast<const uint64_t*>(&c->h_it->pad[3]);
+    const uint64_t* word = reinterpret_cast<const uint64_t*>(&c->h_it->seq);
     const int wrc = wait_device(
         c, [&]() { return __atomic_load_n(word, __ATOMIC_ACQUIRE) == want_bits; }, []() { return (uint64_t)0; },
         "iterate");
     if (wrc != ICP_HIP_OK) return wrc;
   }
-  c->lists_zero = true;
-  for (int k = 0; k < 3; k++) c->last_lists[k] = (unsigned int)c->h_it->pad[k];
   const IterDev& h = *c->h_it;
-  c->last_wide = h.n_wide;
+  c->follow.published(record_lists(h.lists), h.n_wide);
   c->last_cull_path = h.cull_mode != 0.0 ? 1 : 0;
   stats_from_record(c, h, out);
   c->have_results = true;
@@ -340,12 +333,11 @@ int icp_hip_loop_run(icp_hip_ctx* c, icp::SessionCore* core, const icp::SessionP
   if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("device loop: ") + hipGetErrorString(e));
   *core = c->h_loop->core;
   std::memcpy(recs, c->h_ring, (size_t)k * sizeof(icp::LoopRec));
-  c->lists_zero = true;
+  c->follow.counts_zero = true;  // every iteration's publish cleared them
   c->have_results = true;
   for (int j = k - 1; j >= 0; j--)
     if (recs[j].outcome != icp::kStepNone) {
-      for (int q = 0; q < 3; q++) c->last_lists[q] = (unsigned int)recs[j].lists[q];
-      c->last_wide = (double)recs[j].pad[0];
+      c->follow.published(record_lists(recs[j].lists), (double)recs[j].n_wide);
       break;
     }
   if (step_ms) {

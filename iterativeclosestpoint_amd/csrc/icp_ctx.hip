@@ -158,7 +158,7 @@ int icp_hip_create_ex(icp_hip_ctx** out, int device, const icp_hip_config* cfg) 
       hipHostMalloc(reinterpret_cast<void**>(&c->h_it), sizeof(IterDev), hipHostMallocMapped | hipHostMallocCoherent) !=
           hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_it_dev), c->h_it, 0) != hipSuccess ||
-      dalloc(&c->counters, 2) != hipSuccess || dalloc(&c->fb_count, 8) != hipSuccess ||
+      dalloc(&c->counters, 2) != hipSuccess || c->follow.alloc(-1) != hipSuccess ||
       dalloc(&c->loopd, 1) != hipSuccess ||
       dalloc(&c->tickets, (size_t)ticket_words()) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&c->h_loop), sizeof(LoopDev)) != hipSuccess ||
@@ -170,11 +170,9 @@ int icp_hip_create_ex(icp_hip_ctx** out, int device, const icp_hip_config* cfg) 
     return fail(ICP_HIP_ENOMEM, "context allocation failed");
   }
   (void)hipMemset(c->it, 0, sizeof(IterDev));
-  (void)hipMemset(c->fb_count, 0, 8 * sizeof(unsigned int));
   (void)hipMemset(c->tickets, 0, (size_t)ticket_words() * sizeof(unsigned int));
   if (c->dbg) (void)hipMemset(c->dbg, 0, ICP_DBG_SLOTS * sizeof(unsigned long long));
   std::memset(c->h_it, 0, sizeof(IterDev));
-  c->lists_zero = true;
   if (!conf.no_warmup) warm_kernels(device, conf);
   *out = c;
   return ICP_HIP_OK;
@@ -195,7 +193,7 @@ void icp_hip_destroy(icp_hip_ctx* c) {
   free_target(c);
   dfree(c->it);
   dfree(c->counters);
-  dfree(c->fb_count);
+  c->follow.release(true);
   dfree(c->tickets);
   dfree(c->dbg);
   dfree(c->gm);

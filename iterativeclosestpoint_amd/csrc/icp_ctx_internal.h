@@ -26,6 +26,49 @@ struct Prewalk {
   uint32_t stamp = 0;
 };
 
+// The search's follow-up lists as the context holds them (follow_lists.h): the counters for the
+// context's lifetime, the lists for the resident source's, and what the last search published.
+struct FollowBuffers {
+  icp::FollowCounts* counts = nullptr;
+  int32_t* ints = nullptr;    // follow_list_ints(n_src) ints: the four lists (carve_follow_lists)
+  double* guesses = nullptr;  // n_src: the ball list's distance guesses
+  // The counters are zero at every search's launch. An iterate's publish clears them on the device
+  // once it has read them (published()), so the next search needs no memset; after anything else
+  // that ran a search (nn), begin_search clears them itself.
+  bool counts_zero = false;
+  icp::PublishedLists last{0, 0, 0};  // of the last search (icp_iter_stats' three counts)
+  double last_wide = 0.0;             // waves whose candidate set overflowed in the last published iterate
+
+  // The counters at the first call (zeroed), and the lists of a source of n points (n < 0: none).
+  hipError_t alloc(int64_t n) {
+    release(false);
+    hipError_t e = hipSuccess;
+    if (!counts) {
+      e = dalloc(&counts, 1);
+      if (e == hipSuccess) e = hipMemset(counts, 0, sizeof(icp::FollowCounts));
+      counts_zero = e == hipSuccess;
+    }
+    if (e == hipSuccess && n >= 0) e = dalloc(&ints, (size_t)icp::follow_list_ints(n));
+    if (e == hipSuccess && n >= 0) e = dalloc(&guesses, (size_t)n);
+    return e;
+  }
+  void release(bool with_counts) {
+    dfree(ints);
+    dfree(guesses);
+    if (with_counts) dfree(counts);
+  }
+  hipError_t begin_search(hipStream_t s) {
+    const hipError_t e = counts_zero ? hipSuccess : hipMemsetAsync(counts, 0, sizeof(icp::FollowCounts), s);
+    counts_zero = false;
+    return e;
+  }
+  void published(const icp::PublishedLists& lists, double wide) {
+    counts_zero = true;
+    last = lists;
+    last_wide = wide;
+  }
+};
+
 struct icp_hip_ctx {
   // --- configuration and lifetime (icp_ctx.hip)
   int device = 0;
@@ -66,8 +109,7 @@ struct icp_hip_ctx {
   int32_t* perm = nullptr;
   int32_t* pos = nullptr;  // leaf-order position of the match
   double* dist = nullptr;  // residual
-  int32_t* fb_list = nullptr;            // exact, ball and per-lane query lists (3 x n_src)
-  double* fb_u = nullptr;                // the ball list's distance guesses
+  FollowBuffers follow;                  // the search's follow-up lists and counters
   icp::WaveBox* wc_box = nullptr;        // the wave search's candidate cache (one per wave)
   float4* wc_ents = nullptr;
   uint32_t wc_gen = 1;                   // bumped by set_target / set_source (records of older
@@ -91,19 +133,15 @@ struct icp_hip_ctx {
   int8_t xtimed[kTimingRing] = {};  // 0 not timed, 1 events (RCCL), 2 host clock
   double xhost_ms[kTimingRing] = {};
   int64_t n_iterates = 0;
-  unsigned int* fb_count = nullptr;
   unsigned int* tickets = nullptr;  // "last block done" counters of the moments and cull launches
                                     // (zero between launches: the last block resets its own)
   unsigned long long* dbg = nullptr;
-  unsigned int last_lists[3] = {0, 0, 0};  // exact / ball / per-lane list sizes of the last search
-  double last_wide = 0.0;  // waves whose candidate set overflowed in the last published iterate
   int last_cull_path = -1;         // IterDev::cull_mode of the last host-published iterate
-  bool lists_zero = true;               // fb_count is zero (reset by each iteration's publish)
   // per-iteration record
   icp::IterDev* it = nullptr;
   icp::IterDev* h_it = nullptr;      // pinned, coherent: the publishing kernel stores into it
   icp::IterDev* h_it_dev = nullptr;  // its device address
-  uint64_t publish_seq = 0;          // h_it->pad[3] = seq once the record is complete
+  uint64_t publish_seq = 0;          // h_it->seq = this once the record is complete
   // the device-resident loop (icp_hip_loop_run): the session state on the device, its pinned
   // staging copy, and one LoopRec per iteration of a batch (pinned, written by the last kernel)
   static constexpr int kLoopRing = kTimingRing;
@@ -171,7 +209,6 @@ void plane_free_target(icp_hip_ctx* c);  // free_target's part: the normals and 
 void las_destroy(icp_hip_ctx* c);  // the staging buffers released (icp_hip_destroy)
 
 // --- ctx_iterate.cpp
-int32_t* wide_list(int32_t* fbl, int64_t n);  // the wide pass's list inside fb_list (3 n + 64 ints)
 // The device-resident loop: k iterations (k <= kLoopRing) enqueued back to back, each one's last
 // kernel stepping the session on the device (session_step.h), one host wait per batch. core is
 // the session state (uploaded, then updated), recs gets the k iterations' records (outcome

@@ -4,9 +4,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/icp_hip.h"
+#include "follow_lists.h"
 #include "icp_common.h"
 #include "session_step.h"
 
@@ -37,8 +39,11 @@ struct IterDev {
   double fz_sh[6];
   double cull_mode;  // this iterate: 1 = the search's wave records + the band pairs, 0 = full cull
   double n_wide;     // this iterate: waves of the wave search whose candidate set overflowed
-  double pad[4];
+  double lists[3];   // this iterate: published_lists (follow_lists.h) of the search: exact, ball, per-lane
+  double seq;        // host copy only: IterPublish::seq, stored last (the host polls this word)
 };
+static_assert(sizeof(IterDev) == 656, "82 doubles");
+static_assert(offsetof(IterDev, seq) + sizeof(double) == sizeof(IterDev), "seq is the record's last word");
 
 // One wave's covariance record, written by the wave search's epilogue when the band is set
 // (wave_stats.h): the canonical sums of its pairs with d <= fz_lo (s: d^2, a - s, b - t, the 9
@@ -91,16 +96,7 @@ struct NNLaunch {
   int apply;
   int count;                // reference-order kernel counting the reference DFS's work
   int search;               // ICP_SEARCH_CERTIFIED (wave search) / ICP_SEARCH_REFERENCE
-  int32_t* fb_list;         // queries sent to the exact reference-order DFS
-  int32_t* fb_list2;        // queries a wave did not take -> ball search
-  double* fb_u2;            // the distance guess u of each fb_list2 entry
-  unsigned int* fb_count;   // [0] exact list, [1] ball list sizes; [2] per-lane searches, [3] DFS
-                            // finishes of the ball search (counts); [4] half list size; [5] wide
-                            // list size; [6] overflowed waves of the wave search; zero at the launch
-  int32_t* fb_list3;        // 32-query halves of overflowed waves, (half id, lane mask) pairs
-                            // (null: no half pass)
-  int32_t* fb_list4;        // the wide pass (k_nn_wide): overflowed waves / halves as (first query,
-                            // lane mask low, high) triples; null: overflowed lanes take the ball search
+  FollowLists follow;       // the follow-up lists and their counters (follow_lists.h)
   hipEvent_t ev_start;      // optional: the main search kernel's start and end, recorded by its
   hipEvent_t ev_fast_done;  // own dispatch (hipExtLaunchKernel: no marker packets between kernels)
   int have_prev;            // dist_out holds the previous residuals of these queries
@@ -134,6 +130,9 @@ struct NNLaunch {
   unsigned int* pw_count;   // their number (may exceed pw_cap: entries past it were dropped)
   unsigned int pw_cap;      // capacity of pw_list
 };
+// (the launch record is a kernel argument: its layout is part of every search kernel's code)
+static_assert(sizeof(NNLaunch) == 520 && offsetof(NNLaunch, ev_start) == 272,
+              "NNLaunch's layout moved");
 
 // Threads per block of the per-thread search kernels for a given stack depth.
 int nn_block_threads(int levels);
@@ -195,12 +194,12 @@ hipError_t launch_moments_tail(const double* dist, int64_t n, Moments* part, con
 hipError_t launch_finalize_moments(const Moments* gathered, int nranks, IterDev* it, MomentsFinalize fin,
                                    const CullLaunch& cl, hipStream_t s);
 
-// Where the finished record goes: a device-visible pinned host IterDev (list sizes in pad[0..2]);
-// the three list counters are reset for the next search.
+// Where the finished record goes: a device-visible pinned host IterDev (the search's
+// published_lists in IterDev::lists); the search's counters are cleared for the next search.
 struct IterPublish {
   IterDev* host;
-  unsigned int* lists;
-  double seq;  // stored last into host->pad[3]: the record is complete
+  FollowCounts* lists;
+  double seq;  // stored last into host->seq: the record is complete
   // device loop (host null): the session steps on the device and the iteration's LoopRec goes
   // to `rec` (pinned host memory, read after the batch)
   LoopDev* loop;

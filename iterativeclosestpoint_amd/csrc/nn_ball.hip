@@ -102,7 +102,7 @@ __device__ __forceinline__ bool lane_query(const NNLaunch& a, int64_t i, unsigne
     a.dist_out[i] = __builtin_sqrt(best);
   } else {
     exact_query(a, i, st, bs);
-    atomicAdd(a.fb_count + 3, 1u);  // a DFS finish of the ball search
+    atomicAdd(&a.follow.n->dfs_finishes, 1u);  // a DFS finish of the ball search
     if (a.dbg) atomicAdd(&a.dbg[ICP_DBG_LANE_EXACT], 1ull);
   }
   return true;
@@ -269,6 +269,7 @@ __device__ __forceinline__ int wave_bb(const NNLaunch& a, int64_t i, double u, i
 
 __global__ void __launch_bounds__(64) k_nn_ball(NNLaunch a) {
   if (a.loop && a.loop->core.done) return;
+  const FollowLists& L = a.follow;
   extern __shared__ __attribute__((aligned(16))) unsigned long long lds_raw[];
   const int lane = threadIdx.x, g = lane / kBallGL, gl = lane % kBallGL, gbase = g * kBallGL;
   int32_t* stack = reinterpret_cast<int32_t*>(lds_raw) + g * kBallGStack;
@@ -276,9 +277,9 @@ __global__ void __launch_bounds__(64) k_nn_ball(NNLaunch a) {
   // The exact list (queries the wave search could not certify): complete when this kernel starts,
   // one thread each, a DFS stack of `levels` entries per thread in LDS.
   {
-    const unsigned n0 = a.fb_count[0];
+    const unsigned n0 = L.n->exact;
     for (unsigned j = blockIdx.x * 64u + (unsigned)lane; j < n0; j += gridDim.x * 64u)
-      exact_query(a, a.fb_list[j], lds_raw + lane, 64);
+      exact_query(a, L.exact[j], lds_raw + lane, 64);
     wave_lds_fence();
   }
   // The follow-ups of the ball queries (a per-lane certified search, or the reference-order DFS)
@@ -318,7 +319,7 @@ __global__ void __launch_bounds__(64) k_nn_ball(NNLaunch a) {
       // DFS on lane 0, in the same area
       if (wave_bb(a, iq, uq, reinterpret_cast<int32_t*>(lds_raw), lane) != kBBDone && lane == 0) {
         exact_query(a, iq, lds_raw, 1);
-        atomicAdd(a.fb_count + 3, 1u);
+        atomicAdd(&L.n->dfs_finishes, 1u);
         if (a.dbg) atomicAdd(&a.dbg[ICP_DBG_LANE_EXACT], 1ull);
       }
       wave_lds_fence();
@@ -326,7 +327,7 @@ __global__ void __launch_bounds__(64) k_nn_ball(NNLaunch a) {
     qn = 0;
     wave_lds_fence();
   };
-  const unsigned cnt = a.fb_count[1];
+  const unsigned cnt = L.n->ball;
   // Direct mode: each wave takes whole queries, one after the other, with all its lanes: the
   // cooperative search started from the cell tables of the query's bound (a few 64-node steps
   // instead of the 16-lane ball walk and the follow-ups after it). Used for a long list (over four
@@ -348,15 +349,15 @@ __global__ void __launch_bounds__(64) k_nn_ball(NNLaunch a) {
       wave_lds_fence();
       if (lane < dq) exact_query(a, fq[lane], lds_raw + lane, 64);
       if (lane == 0) {
-        atomicAdd(a.fb_count + 3, (unsigned)dq);
+        atomicAdd(&L.n->dfs_finishes, (unsigned)dq);
         if (a.dbg) atomicAdd(&a.dbg[ICP_DBG_LANE_EXACT], (unsigned long long)dq);
       }
       dq = 0;
       wave_lds_fence();
     };
     for (unsigned j = blockIdx.x; j < cnt; j += gridDim.x, ++taken) {
-      const int64_t i = a.fb_list2[j];
-      const double u = a.fb_u2[j];
+      const int64_t i = L.ball[j];
+      const double u = L.ball_u[j];
       if (wave_bb(a, i, u, reinterpret_cast<int32_t*>(lds_raw), lane) != kBBDone) {
         wave_lds_fence();
         if (lane == 0) fq[dq] = (int32_t)i;
@@ -367,7 +368,7 @@ __global__ void __launch_bounds__(64) k_nn_ball(NNLaunch a) {
     if (dq > 0) dfs_flush();
     // the queries taken by the cooperative search count as follow-up searches, as after the ball
     // walk (icp_iter_stats.n_lane_search)
-    if (lane == 0 && taken > 0) atomicAdd(a.fb_count + 2, taken);
+    if (lane == 0 && taken > 0) atomicAdd(&L.n->lane_searches, taken);
     return;
   }
   for (unsigned j0 = blockIdx.x * kBallGroups; j0 < cnt; j0 += gridDim.x * kBallGroups) {
@@ -377,8 +378,8 @@ __global__ void __launch_bounds__(64) k_nn_ball(NNLaunch a) {
     int64_t i = 0;
     double u = 0.0, qx = 0.0, qy = 0.0, qz = 0.0;
     if (live) {
-      i = a.fb_list2[j];
-      u = a.fb_u2[j];
+      i = L.ball[j];
+      u = L.ball_u[j];
       qx = a.x[i];
       qy = a.y[i];
       qz = a.z[i];
@@ -498,7 +499,7 @@ __global__ void __launch_bounds__(64) k_nn_ball(NNLaunch a) {
     const bool fol = follow != 0 && gl == 0;
     const unsigned long long fm = wballot(fol);
     if (fol) {
-      atomicAdd(a.fb_count + (follow == 1 ? 2 : 3), 1u);  // counted for the iteration record
+      atomicAdd(follow == 1 ? &L.n->lane_searches : &L.n->dfs_finishes, 1u);  // counted for the iteration record
       fq[qn + mask_rank(fm)] = (int32_t)i | (follow << 30);
       // an overflowing ball's guess bounds the nearest distance (a guess the ball did not cover
       // does not, nor does an unusable one)
@@ -670,7 +671,7 @@ hipError_t launch_nn_follow(const NNLaunch& a, hipStream_t s) {
   b.ball_queue_off = (int32_t)bshm;  // the follow-up queue (64 entries + guesses) after the stacks and lists
   // after the wide pass the list holds what it left: far queries (lanes that joined no box, and
   // lanes the wide pass could not certify, with its bounds): whole queries per wave
-  if (a.fb_list4 && b.ball_mode == 0) b.ball_mode = 2;
+  if (a.follow.wide && b.ball_mode == 0) b.ball_mode = 2;
   bshm += 64 * (sizeof(int32_t) + sizeof(double));
   hipExtLaunchKernelGGL(k_nn_ball, dim3((unsigned)(bq < 8192 ? bq : 8192)), dim3(64), (uint32_t)bshm, s, nullptr,
                         nullptr, 0u, b);

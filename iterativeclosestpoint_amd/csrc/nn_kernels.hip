@@ -259,6 +259,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
   static_assert(!(HALF && WIDE), "one second pass per instance");
   static_assert(!kPre || (APPLY && !CERT && !kSecond), "the prewalk: the lead's transform, no queries");
   const bool active = !kPre && i < a.n;
+  const FollowLists& L = a.follow;  // what this wave hands to later kernels (follow_lists.h)
   int32_t* queue = reinterpret_cast<int32_t*>(wl);
   double4* stage = reinterpret_cast<double4*>(wl);  // after the walk only
   int32_t* plist = queue + kWaveQueue;               // candidate points
@@ -452,7 +453,7 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
           qat(a.pos_out, i) = pos;
           qat(a.dist_out, i) = d;
         }
-        wave_append_u(active && finite_q && !safe, i, u, a.fb_count + 1, a.fb_list2, a.fb_u2);
+        wave_append_u(active && finite_q && !safe, i, u, &L.n->ball, L.ball, L.ball_u);
       }
       if (!kSecond) wave_record<DBG>(a, wid, lane, active, safe || !finite_q, d, pos, qx, qy, qz, wl);
       return;
@@ -955,26 +956,22 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
   // balls; an overflowing half hands its queries to the ball search.
   bool deferred = false;
   if (!kPre && overflow) {
-    if (!kSecond && lane == 0) atomicAdd(a.fb_count + 6, 1u);  // the iteration record's n_wide
-    if (!HALF && !kCache && a.fb_list3 != nullptr) {  // the half pass: first iterates only
+    if (!kSecond && lane == 0) atomicAdd(&L.n->overflowed, 1u);  // the iteration record's n_wide
+    if (!HALF && !kCache && L.halves != nullptr) {  // the half pass: first iterates only
       // entries (half id, mask of its deferred lanes): the half pass searches exactly these
       const unsigned long long dm = wballot(join);
       deferred = join;
       const unsigned nh = ((uint32_t)dm != 0u ? 1u : 0u) + ((dm >> 32) != 0ull ? 1u : 0u);
       if (lane == 0 && nh > 0) {
-        unsigned at = atomicAdd(a.fb_count + 4, nh);
+        unsigned at = atomicAdd(&L.n->halves, nh);
         if ((uint32_t)dm != 0u) {
-          a.fb_list3[2 * at] = (int32_t)(2 * wid);
-          a.fb_list3[2 * at + 1] = (int32_t)(uint32_t)dm;
+          push_half(L.halves, at, HalfEntry{(int32_t)(2 * wid), (uint32_t)dm});
           at++;
         }
-        if ((dm >> 32) != 0ull) {
-          a.fb_list3[2 * at] = (int32_t)(2 * wid + 1);
-          a.fb_list3[2 * at + 1] = (int32_t)(uint32_t)(dm >> 32);
-        }
+        if ((dm >> 32) != 0ull) push_half(L.halves, at, HalfEntry{(int32_t)(2 * wid + 1), (uint32_t)(dm >> 32)});
         if (kDbg && a.dbg) atomicAdd(&a.dbg[ICP_DBG_HALVES], (unsigned long long)nh);
       }
-    } else if (!WIDE && a.fb_list4 != nullptr) {
+    } else if (!WIDE && L.wide != nullptr) {
       // the wide pass (k_nn_wide) searches the joined lanes again with the same box, walked and
       // scanned in segments: (first query of the wave or half, lane mask) per entry
       const unsigned long long dm = wballot(join);
@@ -983,10 +980,8 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
         const int fl = __builtin_ctzll(dm);
         const int32_t base = __builtin_amdgcn_readlane(i, fl) - fl;  // i = base + lane
         if (lane == 0) {
-          const unsigned at = atomicAdd(a.fb_count + 5, 1u);
-          a.fb_list4[3 * at] = base;
-          a.fb_list4[3 * at + 1] = (int32_t)(uint32_t)dm;
-          a.fb_list4[3 * at + 2] = (int32_t)(uint32_t)(dm >> 32);
+          const unsigned at = atomicAdd(&L.n->wide, 1u);
+          push_wide(L.wide, at, WideEntry{base, (uint32_t)dm, (uint32_t)(dm >> 32)});
         }
       }
     }
@@ -1526,10 +1521,10 @@ __device__ __forceinline__ void wave_search(const NNLaunch& a, const int32_t i, 
       qat(a.dist_out, i) = d;
     }
   }
-  wave_append(to_exact, i, a.fb_count, a.fb_list);
+  wave_append(to_exact, i, &L.n->exact, L.exact);
   const bool covered = !(join && !(best <= u));
-  wave_append_u(to_lane, i, (WIDE && wide_lane) ? gw : covered ? u : __builtin_inf(), a.fb_count + 1, a.fb_list2,
-                a.fb_u2);
+  wave_append_u(to_lane, i, (WIDE && wide_lane) ? gw : covered ? u : __builtin_inf(), &L.n->ball, L.ball,
+                L.ball_u);
   PSTOP(6);
   if (!kSecond)
     wave_record<DBG>(a, wid, lane, active, safe || written, safe ? __builtin_sqrt(u) : d, safe ? prev_pos : pos, qx,
@@ -1594,12 +1589,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
   extern __shared__ __attribute__((aligned(16))) unsigned long long lds_raw[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   unsigned char* wl = reinterpret_cast<unsigned char*>(lds_raw) + wv * kWaveLds;
-  const unsigned cnt = a.fb_count[4];
+  const FollowLists& L = a.follow;
+  const unsigned cnt = L.n->halves;
   const unsigned waves = gridDim.x * (blockDim.x >> 6);
   for (unsigned j = blockIdx.x * (blockDim.x >> 6) + wv; j < cnt; j += waves) {
-    const int32_t hb = a.fb_list3[2 * j];
-    const uint32_t mask = (uint32_t)a.fb_list3[2 * j + 1];  // the lanes the first pass deferred
-    const int64_t q = (int64_t)hb * 32 + lane;
+    const HalfEntry e = read_half(L.halves, j);  // e.lanes: the lanes the first pass deferred
+    const uint32_t mask = e.lanes;
+    const int64_t q = (int64_t)e.half * 32 + lane;
     const int32_t i = (lane < 32 && ((mask >> lane) & 1u) && q < a.n) ? (int32_t)q : (int32_t)a.n;
     wave_lds_fence();  // the previous half's LDS reads are done
     wave_search<false, NG, false, true, DBG>(a, i, lane, wl);
@@ -1622,12 +1618,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ICP_WI
   extern __shared__ __attribute__((aligned(16))) unsigned long long lds_raw[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   unsigned char* wl = reinterpret_cast<unsigned char*>(lds_raw) + wv * kWideLds;
-  const unsigned cnt = a.fb_count[5];
+  const FollowLists& L = a.follow;
+  const unsigned cnt = L.n->wide;
   const unsigned waves = gridDim.x * (blockDim.x >> 6);
   for (unsigned j = blockIdx.x * (blockDim.x >> 6) + wv; j < cnt; j += waves) {
-    const int64_t base = a.fb_list4[3 * j];
-    const unsigned long long mask =
-        (unsigned long long)(uint32_t)a.fb_list4[3 * j + 1] | (unsigned long long)(uint32_t)a.fb_list4[3 * j + 2] << 32;
+    const WideEntry e = read_wide(L.wide, j);
+    const int64_t base = e.first;
+    const unsigned long long mask = (unsigned long long)e.lanes_lo | (unsigned long long)e.lanes_hi << 32;
     const int64_t q = base + lane;
     const int32_t i = (((mask >> lane) & 1ull) && q < a.n) ? (int32_t)q : (int32_t)a.n;
     wave_lds_fence();  // the previous entry's LDS reads are done
@@ -1782,10 +1779,10 @@ hipError_t launch_nn(const NNLaunch& a, hipStream_t s) {
         else wave(k_nn_wave<false, G, C, D, 0>);
       });
       // the half pass over the overflowed waves
-      if (a.fb_list3)
+      if (a.follow.halves)
         hipExtLaunchKernelGGL((k_nn_half<G, D>), dim3(hgrid), dim3(256), (uint32_t)wshm, s, nullptr, nullptr, 0u, h);
       // the wide pass over the overflowed waves and halves
-      if (a.fb_list4)
+      if (a.follow.wide)
         hipExtLaunchKernelGGL((k_nn_wide<G, D>), dim3(ggrid), dim3(256), (uint32_t)gshm, s, nullptr, nullptr, 0u, h);
     });
   });

@@ -437,7 +437,7 @@ __device__ void loop_step(LoopDev* L, const IterDev& r, LoopRec* out) {
   for (int k = 0; k < 3; k++) {
     out->ma[k] = r.c_global.ma[k];
     out->mb[k] = r.c_global.mb[k];
-    out->lists[k] = r.pad[k];
+    out->lists[k] = r.lists[k];
   }
   for (int k = 0; k < 9; k++) out->H[k] = r.c_global.c[k];
   SessionCore core = L->core;
@@ -450,7 +450,7 @@ __device__ void loop_step(LoopDev* L, const IterDev& r, LoopRec* out) {
     L->core = core;
   }
   out->outcome = outcome;
-  out->pad[0] = (int32_t)r.n_wide;
+  out->n_wide = (int32_t)r.n_wide;
   for (int k = 0; k < 16; k++) {
     out->T[k] = core.T[k];
     out->Tc[k] = core.Tc[k];
@@ -462,13 +462,12 @@ __device__ void loop_step(LoopDev* L, const IterDev& r, LoopRec* out) {
 // completes it, the block stores it with system-scope relaxed stores, every thread waits for its
 // stores to be acknowledged, then thread 0 stores the sequence word. No system-scope release
 // fence: it would write back the whole L2, which the search has just dirtied with megabytes. The
-// list sizes ride along (pad[0..2]) and are reset for the next search.
+// search's published_lists ride along (IterDev::lists) and its counters are cleared for the next search.
 // LOOP = false: an instance without the device loop's step (the session decisions and the 3x3
 // SVD): the cull kernel's fused tail, whose registers count for every cull block.
 template <bool LOOP = true>
 __device__ void finalize_cov_publish(IterDev* it, const CovMoments& g, IterPublish pub, IterDev* rec) {
-  constexpr int kWords = (int)(sizeof(IterDev) / sizeof(double)) - 1;  // all but pad[3], the flag
-  static_assert(offsetof(IterDev, pad) + 3 * sizeof(double) == kWords * sizeof(double), "flag is the last word");
+  constexpr int kWords = (int)(offsetof(IterDev, seq) / sizeof(double));  // all but seq, the flag (the last word)
   double* rw = reinterpret_cast<double*>(rec);
   const double* iw = reinterpret_cast<const double*>(it);
   for (int k = threadIdx.x; k < kWords + 1; k += blockDim.x) rw[k] = iw[k];  // the device record, in parallel
@@ -476,12 +475,12 @@ __device__ void finalize_cov_publish(IterDev* it, const CovMoments& g, IterPubli
   if (threadIdx.x == 0) {
     rec->c_global = g;
     rec->rmse = (g.n > 0) ? __builtin_sqrt(g.sum_d2 / g.n) : 0.0;  // icpengine.cpp:274-278
-    // exact (the wave search's list + the ball search's DFS finishes), ball, per-lane
-    rec->pad[0] = (double)(pub.lists[0] + pub.lists[3]);
-    rec->pad[1] = (double)pub.lists[1];
-    rec->pad[2] = (double)pub.lists[2];
-    rec->n_wide = (double)pub.lists[6];
-    for (int k = 0; k < 7; k++) pub.lists[k] = 0u;  // + the half and wide lists, overflowed waves
+    const PublishedLists pl = published_lists(*pub.lists);
+    rec->lists[0] = (double)pl.exact;
+    rec->lists[1] = (double)pl.ball;
+    rec->lists[2] = (double)pl.lane;
+    rec->n_wide = (double)pub.lists->overflowed;
+    clear_counts(pub.lists);
     it->c_global = rec->c_global;
     it->rmse = rec->rmse;
     band_next(it);
@@ -494,7 +493,7 @@ __device__ void finalize_cov_publish(IterDev* it, const CovMoments& g, IterPubli
     __hip_atomic_store(dst + k, rw[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(&pub.host->pad[3], pub.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (threadIdx.x == 0) __hip_atomic_store(&pub.host->seq, pub.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // The last level of the covariance sums: the merged part sums -> it->c_local; with finalize (one

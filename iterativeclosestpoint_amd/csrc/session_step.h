@@ -112,7 +112,9 @@ struct LoopRec {
   double T[16], Tc[16];
   int32_t outcome;  // StepOutcome (kStepNone: the session was already done)
   int32_t iter;     // the iteration index (0-based)
-  int32_t pad[2];
+  int32_t n_wide;   // IterDev::n_wide: waves of the search whose candidate set overflowed
+  int32_t pad;
 };
+static_assert(sizeof(LoopRec) == 496, "62 doubles");
 
 }  // namespace icp
