@@ -34,8 +34,8 @@ extern "C" {
 
 #define ICP_HIP_OK 0
 #define ICP_HIP_EINVAL (-1)
-#define ICP_HIP_ENOMEM (-2)
-#define ICP_HIP_EDEVICE (-3)
+#define ICP_HIP_ENOMEM (-2)  /* a device allocation failed (hipErrorOutOfMemory), wherever in a call */
+#define ICP_HIP_EDEVICE (-3) /* any other HIP error */
 #define ICP_HIP_ERCCL (-4)
 #define ICP_HIP_ENOTREADY (-5)
 #define ICP_HIP_EEXCHANGE (-6) /* the host-exchange callback (icp_hip_comm_init_host) failed or
@@ -349,7 +349,11 @@ int icp_hip_exchange_timings(icp_hip_ctx* ctx, int k, double* exchange_ms);
  * built on the device (max_depth <= 21, config octree_builder AUTO) or on the host (deeper
  * trees, or ICP_BUILD_HOST); both produce the same arrays bit for bit. rules selects the initial
  * best distance of findNearest. Non-finite target coordinates and empty targets are rejected
- * (ICP_HIP_EINVAL). Replaces Octree::Octree(points, max_pts, max_d), octree.cpp:41-126. */
+ * (ICP_HIP_EINVAL). Replaces Octree::Octree(points, max_pts, max_d), octree.cpp:41-126.
+ * A cloud is installed whole or not at all: a set_target or set_source that fails after its
+ * argument checks (every variant: host, _device, _las) leaves the context without that cloud,
+ * as a new context is (no target: ICP_HIP_ENOTREADY from the calls that need one; no source: an
+ * empty one); the other cloud is untouched. */
 int icp_hip_set_target(icp_hip_ctx* ctx, const double* xyz, int64_t n, int max_points, int max_depth,
                        int rules);
 
@@ -369,7 +373,7 @@ int icp_hip_target_separation(icp_hip_ctx* ctx, float* sep_out);
 /* Upload this rank's source shard (AoS xyz). Queries are reordered on the device along a
  * Morton curve for traversal coherence; every output is returned in the caller's order.
  * A shard holds fewer than 2^29 points (ICP_HIP_EINVAL otherwise; shard larger clouds over a
- * device group). */
+ * device group). Whole or not at all, as icp_hip_set_target. */
 int icp_hip_set_source(icp_hip_ctx* ctx, const double* xyz, int64_t n);
 
 /* One ICP iteration body. If T_apply (row-major 4x4) is non-null, src = T_apply * src is applied

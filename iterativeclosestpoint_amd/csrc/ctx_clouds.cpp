@@ -112,49 +112,30 @@ int check_device_ptr(const icp_hip_ctx* c, const void* p, const char* what, unsi
   return ICP_HIP_OK;
 }
 
-// The host-staged routes of the device variants: the caller's buffer through host memory.
-template <typename T>
-static hipError_t stage_down(const icp_hip_ctx* c, std::vector<T>* h, const T* d, size_t count) {
-  h->resize(count);
-  if (count == 0) return hipSuccess;
-  if (c->group) return hipMemcpy(h->data(), d, count * sizeof(T), hipMemcpyDeviceToHost);
-  hipError_t e = hipMemcpyAsync(h->data(), d, count * sizeof(T), hipMemcpyDeviceToHost, c->stream);
-  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
-}
-
-template <typename T>
-static hipError_t stage_up(const icp_hip_ctx* c, T* d, const std::vector<T>& h) {
-  if (h.empty()) return hipSuccess;
-  if (c->group) return hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-  hipError_t e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
-  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
-}
-
 // set_target after the argument checks, from a host cloud (xyz) or a device cloud (d_in), one of
 // them null. The device builder reads d_in in place; the host builder gets it staged down.
+// Whole or not at all: a failure leaves the context without a target (as free_target leaves it);
+// the source is untouched either way.
 static int set_target_core(icp_hip_ctx* c, const double* xyz, const double* d_in, int64_t n, int max_points,
                            int max_depth, int rules) {
   HIP_TRY(hipSetDevice(c->device));
   free_target(c);
+  ScopeExit undo([c] { free_target(c); });
   HIP_TRY(reset_band(c));
   hipEvent_t e0 = c->ev_it0, e1 = c->ev_it1;
   HIP_TRY(hipEventRecord(e0, c->stream));
   const bool on_device = max_depth <= kGpuBuildMaxDepth && c->cfg.octree_builder == ICP_BUILD_AUTO;
   if (on_device) {
     // device build straight from the AoS cloud in HBM (octree_gpu.hip): the caller's, or the upload
+    DevScratch S;  // the upload: released with this block, before the boxes and tables are made
     double* d_xyz = nullptr;
     if (!d_in) {
-      HIP_TRY(dalloc(&d_xyz, 3 * (size_t)n));
-      hipError_t e = hipMemcpyAsync(d_xyz, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
-      if (e != hipSuccess) {
-        dfree(d_xyz);
-        return fail(ICP_HIP_EDEVICE, std::string("set_target upload: ") + hipGetErrorString(e));
-      }
+      HIP_TRY(S.alloc(&d_xyz, 3 * (size_t)n));
+      HIP_TRY(hipMemcpyAsync(d_xyz, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     }
     GpuOctree t;
     std::string why;
     const int rc = gpu_build_octree(d_in ? d_in : d_xyz, n, max_points, max_depth, c->stream, &t, &why);
-    dfree(d_xyz);
     if (rc != 0) return fail(rc == 1 ? ICP_HIP_EINVAL : rc == -2 ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, why);
     c->nodes = t.nodes;
     c->pts = t.pts;
@@ -213,6 +194,7 @@ static int set_target_core(icp_hip_ctx* c, const double* xyz, const double* d_in
   c->have_prev = false;
   c->wc_gen++;  // cached candidate lists name points of the previous tree
   c->have_results = false;
+  undo.dismiss();
   return ICP_HIP_OK;
 }
 
@@ -342,13 +324,16 @@ int icp_hip_target_info(icp_hip_ctx* c, int64_t* n_nodes, int64_t* n_leaves, int
 // set_source after the argument checks, from a host cloud (xyz) or a device cloud (d_in), one of
 // them null when n > 0. The device query order and the gather read d_in in place; the host query
 // order gets it staged down.
+// Whole or not at all: a failure leaves the context without a source (as free_source leaves it,
+// n_src = 0); the target is untouched either way.
 static int set_source_core(icp_hip_ctx* c, const double* xyz, const double* d_in, int64_t n) {
   // the wave search addresses per-query arrays by 32-bit byte offsets (nn_device.h qat): < 2^29
   // points per shard (12 GB of coordinates; a larger cloud is sharded over a device group)
   if (n >= ((int64_t)1 << 29)) return fail(ICP_HIP_EINVAL, "source shard of 2^29 points or more");
   HIP_TRY(hipSetDevice(c->device));
   free_source(c);
-  c->n_src = n;
+  ScopeExit undo([c] { free_source(c); });
+  c->n_src = n;  // the allocations below are sized by it (prewalk_new_source); the guard restores 0
   c->nb_mom = moments_num_parts(n);
   c->nb_cull = cull_num_blocks(n);
   HIP_TRY(dalloc(&c->x, n));
@@ -378,38 +363,36 @@ static int set_source_core(icp_hip_ctx* c, const double* xyz, const double* d_in
     dfree(c->wstat);
   }
   HIP_TRY(reset_band(c));
-  if (n == 0) return ICP_HIP_OK;
-  // Spatially compact query order (kd buckets of 64 = one wave): on the device from the uploaded
-  // cloud (query_order_gpu.hip), or on the host (config query_order = 1)
-  double* scratch = nullptr;
-  const double* aos = d_in;
-  hipError_t e = hipSuccess;
-  if (!d_in) {
-    e = dalloc(&scratch, 3 * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpyAsync(scratch, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
-    aos = scratch;
-  }
-  if (e == hipSuccess) {
+  if (n > 0) {
+    // Spatially compact query order (kd buckets of 64 = one wave): on the device from the uploaded
+    // cloud (query_order_gpu.hip), or on the host (config query_order = 1)
+    DevScratch S;
+    const double* aos = d_in;
+    if (!d_in) {
+      double* up = nullptr;
+      HIP_TRY(S.alloc(&up, 3 * (size_t)n));
+      HIP_TRY(hipMemcpyAsync(up, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+      aos = up;
+    }
     if (c->cfg.query_order == 0) {
-      e = gpu_kd_query_order(aos, n, 8, c->perm, c->stream);
+      HIP_TRY(gpu_kd_query_order(aos, n, 8, c->perm, c->stream));
     } else {
       std::vector<double> staged;
       if (!xyz) {
-        e = stage_down(c, &staged, d_in, 3 * (size_t)n);
+        HIP_TRY(stage_down(c, &staged, d_in, 3 * (size_t)n));
         xyz = staged.data();
       }
       std::vector<int32_t> perm;
-      if (e == hipSuccess) kd_query_order(xyz, n, 8, &perm);
-      if (e == hipSuccess) e = hipMemcpyAsync(c->perm, perm.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host order is read by the copy
+      kd_query_order(xyz, n, 8, &perm);
+      HIP_TRY(hipMemcpyAsync(c->perm, perm.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));  // the host order is read by the copy
     }
+    HIP_TRY(launch_gather_deinterleave(aos, c->perm, c->x, c->y, c->z, n, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->have_results = false;
+    c->have_prev = false;
   }
-  if (e == hipSuccess) e = launch_gather_deinterleave(aos, c->perm, c->x, c->y, c->z, n, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(scratch);
-  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("set_source: ") + hipGetErrorString(e));
-  c->have_results = false;
-  c->have_prev = false;
+  undo.dismiss();
   return ICP_HIP_OK;
 }
 
@@ -446,13 +429,12 @@ int icp_hip_get_source(icp_hip_ctx* c, double* xyz_out) {
   if (!c || (!xyz_out && c->n_src > 0)) return fail(ICP_HIP_EINVAL, "null argument");
   if (c->n_src == 0) return ICP_HIP_OK;
   HIP_TRY(hipSetDevice(c->device));
+  DevScratch S;
   double* aos = nullptr;
-  HIP_TRY(dalloc(&aos, 3 * (size_t)c->n_src));
-  hipError_t e = launch_scatter_aos(c->perm, c->x, c->y, c->z, aos, c->n_src, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(xyz_out, aos, 3 * sizeof(double) * c->n_src, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(aos);
-  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("get_source: ") + hipGetErrorString(e));
+  HIP_TRY(S.alloc(&aos, 3 * (size_t)c->n_src));
+  HIP_TRY(launch_scatter_aos(c->perm, c->x, c->y, c->z, aos, c->n_src, c->stream));
+  HIP_TRY(hipMemcpyAsync(xyz_out, aos, 3 * sizeof(double) * c->n_src, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return ICP_HIP_OK;
 }
 
@@ -468,9 +450,8 @@ int icp_hip_get_source_device(icp_hip_ctx* c, double* d_xyz_out) {
   }
   if (c->n_src == 0) return ICP_HIP_OK;
   HIP_TRY(hipSetDevice(c->device));
-  hipError_t e = launch_scatter_aos(c->perm, c->x, c->y, c->z, d_xyz_out, c->n_src, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("get_source_device: ") + hipGetErrorString(e));
+  HIP_TRY(launch_scatter_aos(c->perm, c->x, c->y, c->z, d_xyz_out, c->n_src, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return ICP_HIP_OK;
 }
 
@@ -480,18 +461,15 @@ int icp_hip_get_correspondences(icp_hip_ctx* c, int32_t* idx_out, double* dist_o
   if (!c->have_results) return fail(ICP_HIP_ENOTREADY, "no iteration has run on this source");
   if (c->n_src == 0) return ICP_HIP_OK;
   HIP_TRY(hipSetDevice(c->device));
+  DevScratch S;
   int32_t* di = nullptr;
   double* dd = nullptr;
-  hipError_t e = hipSuccess;
-  if (idx_out) e = dalloc(&di, c->n_src);
-  if (e == hipSuccess && dist_out) e = dalloc(&dd, c->n_src);
-  if (e == hipSuccess) e = launch_scatter_corr(c->perm, c->pos, c->pts, di, c->dist, dd, c->n_src, c->stream);
-  if (e == hipSuccess && idx_out) e = hipMemcpyAsync(idx_out, di, sizeof(int32_t) * c->n_src, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && dist_out) e = hipMemcpyAsync(dist_out, dd, sizeof(double) * c->n_src, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(di);
-  dfree(dd);
-  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("get_correspondences: ") + hipGetErrorString(e));
+  if (idx_out) HIP_TRY(S.alloc(&di, c->n_src));
+  if (dist_out) HIP_TRY(S.alloc(&dd, c->n_src));
+  HIP_TRY(launch_scatter_corr(c->perm, c->pos, c->pts, di, c->dist, dd, c->n_src, c->stream));
+  if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out, di, sizeof(int32_t) * c->n_src, hipMemcpyDeviceToHost, c->stream));
+  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd, sizeof(double) * c->n_src, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return ICP_HIP_OK;
 }
 
@@ -514,9 +492,8 @@ int icp_hip_get_correspondences_device(icp_hip_ctx* c, int32_t* d_idx_out, doubl
   if (!c->have_results) return fail(ICP_HIP_ENOTREADY, "no iteration has run on this source");
   if (c->n_src == 0 || (!d_idx_out && !d_dist_out)) return ICP_HIP_OK;
   HIP_TRY(hipSetDevice(c->device));
-  hipError_t e = launch_scatter_corr(c->perm, c->pos, c->pts, d_idx_out, c->dist, d_dist_out, c->n_src, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("get_correspondences_device: ") + hipGetErrorString(e));
+  HIP_TRY(launch_scatter_corr(c->perm, c->pos, c->pts, d_idx_out, c->dist, d_dist_out, c->n_src, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return ICP_HIP_OK;
 }
 
@@ -540,49 +517,45 @@ static int nn_core(icp_hip_ctx* c, bool dev, const double* q, int64_t n, int32_t
     return ICP_HIP_OK;
   }
   HIP_TRY(hipSetDevice(c->device));
-  double *up = nullptr, *x = nullptr, *y = nullptr, *z = nullptr, *d = nullptr, *dd = nullptr;
-  int32_t *pos = nullptr, *di = nullptr;
-  hipError_t e = hipSuccess;
-  if ((dev || (e = dalloc(&up, 3 * (size_t)n)) == hipSuccess) && (e = dalloc(&x, n)) == hipSuccess &&
-      (e = dalloc(&y, n)) == hipSuccess && (e = dalloc(&z, n)) == hipSuccess && (e = dalloc(&d, n)) == hipSuccess &&
-      (dev || (e = dalloc(&dd, n)) == hipSuccess) && (e = dalloc(&pos, n)) == hipSuccess &&
-      (dev || (e = dalloc(&di, n)) == hipSuccess)) {
-    if (!dev) e = hipMemcpyAsync(up, q, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
-    const double* aos = dev ? q : up;
-    if (e == hipSuccess) e = launch_deinterleave(aos, x, y, z, n, c->stream);
-    NNLaunch a = base_launch(c);
-    a.x = x;
-    a.y = y;
-    a.z = z;
-    a.pos_out = pos;
-    a.dist_out = d;
-    a.n = n;
-    int32_t* fbl = nullptr;
-    double* fbu = nullptr;
-    if (e == hipSuccess) e = dalloc(&fbl, (size_t)follow_list_ints(n));
-    if (e == hipSuccess) e = dalloc(&fbu, (size_t)n);
-    a.follow = carve_follow_lists(fbl, fbu, c->follow.counts, n, c->cfg.overflow_halves != 0,
-                                  c->cfg.scan32 && c->cfg.wide_pass != 1);
-    FollowCounts counts{};
-    if (e == hipSuccess) e = c->follow.begin_search(c->stream);
-    if (e == hipSuccess) e = launch_nn(a, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&counts, c->follow.counts, sizeof(FollowCounts), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    c->follow.last = published_lists(counts);
-    dfree(fbl);
-    dfree(fbu);
-    if (dev) {
-      // straight into the caller's buffers (either may be null)
-      if (e == hipSuccess && (idx_out || dist_out)) e = launch_scatter_corr(nullptr, pos, c->pts, idx_out, d, dist_out, n, c->stream);
-    } else {
-      if (e == hipSuccess) e = launch_scatter_corr(nullptr, pos, c->pts, di, d, dd, n, c->stream);
-      if (e == hipSuccess && idx_out) e = hipMemcpyAsync(idx_out, di, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream);
-      if (e == hipSuccess && dist_out) e = hipMemcpyAsync(dist_out, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  FollowCounts counts{};  // before its source's owner: outlives the copy
+  DevScratch S;           // the host variant's upload and outputs, the query arrays, the follow-up lists
+  double *up = nullptr, *x = nullptr, *y = nullptr, *z = nullptr, *d = nullptr, *dd = nullptr, *fbu = nullptr;
+  int32_t *pos = nullptr, *di = nullptr, *fbl = nullptr;
+  if (!dev) HIP_TRY(S.alloc(&up, 3 * (size_t)n));
+  HIP_TRY(S.alloc(&x, n));
+  HIP_TRY(S.alloc(&y, n));
+  HIP_TRY(S.alloc(&z, n));
+  HIP_TRY(S.alloc(&d, n));
+  if (!dev) HIP_TRY(S.alloc(&dd, n));
+  HIP_TRY(S.alloc(&pos, n));
+  if (!dev) HIP_TRY(S.alloc(&di, n));
+  if (!dev) HIP_TRY(hipMemcpyAsync(up, q, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_deinterleave(dev ? q : up, x, y, z, n, c->stream));
+  HIP_TRY(S.alloc(&fbl, (size_t)follow_list_ints(n)));
+  HIP_TRY(S.alloc(&fbu, (size_t)n));
+  NNLaunch a = base_launch(c);
+  a.x = x;
+  a.y = y;
+  a.z = z;
+  a.pos_out = pos;
+  a.dist_out = d;
+  a.n = n;
+  a.follow = carve_follow_lists(fbl, fbu, c->follow.counts, n, c->cfg.overflow_halves != 0,
+                                c->cfg.scan32 && c->cfg.wide_pass != 1);
+  HIP_TRY(c->follow.begin_search(c->stream));
+  HIP_TRY(launch_nn(a, c->stream));
+  HIP_TRY(hipMemcpyAsync(&counts, c->follow.counts, sizeof(FollowCounts), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->follow.last = published_lists(counts);
+  if (dev) {
+    // straight into the caller's buffers (either may be null)
+    if (idx_out || dist_out) HIP_TRY(launch_scatter_corr(nullptr, pos, c->pts, idx_out, d, dist_out, n, c->stream));
+  } else {
+    HIP_TRY(launch_scatter_corr(nullptr, pos, c->pts, di, d, dd, n, c->stream));
+    if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out, di, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
   }
-  dfree(up); dfree(x); dfree(y); dfree(z); dfree(d); dfree(dd); dfree(pos); dfree(di);
-  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, std::string("nn: ") + hipGetErrorString(e));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return ICP_HIP_OK;
 }
 

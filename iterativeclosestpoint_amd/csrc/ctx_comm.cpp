@@ -92,13 +92,19 @@ void icp_ctx_abort_comm(icp_hip_ctx* c) {
   (void)hipGetLastError();
 }
 
-int icp_ctx_attach_comm(icp_hip_ctx* c, ncclComm_t comm, int nranks, int rank) {
-  HIP_TRY(hipSetDevice(c->device));
-  icp_ctx_drop_transport(c);
+// The all-gather's receive buffers, one record per rank.
+static int realloc_gather(icp_hip_ctx* c, int nranks) {
   dfree(c->gm);
   dfree(c->gc);
   HIP_TRY(dalloc(&c->gm, (size_t)nranks));
   HIP_TRY(dalloc(&c->gc, (size_t)nranks));
+  return ICP_HIP_OK;
+}
+
+int icp_ctx_attach_comm(icp_hip_ctx* c, ncclComm_t comm, int nranks, int rank) {
+  HIP_TRY(hipSetDevice(c->device));
+  icp_ctx_drop_transport(c);
+  if (const int rc = realloc_gather(c, nranks)) return rc;
   c->comm = comm;
   c->nranks = nranks;
   c->rank = rank;
@@ -148,10 +154,7 @@ int icp_hip_comm_init(icp_hip_ctx* c, int nranks, int rank, const uint8_t id_byt
   HIP_TRY(hipSetDevice(c->device));
   // back to a world of one first: a failure below leaves no stale transport behind
   icp_ctx_drop_transport(c);
-  dfree(c->gm);
-  dfree(c->gc);
-  HIP_TRY(dalloc(&c->gm, (size_t)nranks));
-  HIP_TRY(dalloc(&c->gc, (size_t)nranks));
+  if (const int rc = realloc_gather(c, nranks)) return rc;
   ncclUniqueId id;
   std::memcpy(&id, id_bytes, sizeof(id));
   ncclComm_t comm = nullptr;
@@ -169,10 +172,7 @@ int icp_hip_comm_init_host(icp_hip_ctx* c, int nranks, int rank, icp_hip_exchang
   HIP_TRY(hipSetDevice(c->device));
   icp_ctx_drop_transport(c);
   if (!exchange) return ICP_HIP_OK;  // a world of one without a transport
-  dfree(c->gm);
-  dfree(c->gc);
-  HIP_TRY(dalloc(&c->gm, (size_t)nranks));
-  HIP_TRY(dalloc(&c->gc, (size_t)nranks));
+  if (const int rc = realloc_gather(c, nranks)) return rc;
   c->xfn = exchange;
   c->xuser = user;
   c->nranks = nranks;

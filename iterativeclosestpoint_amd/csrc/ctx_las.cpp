@@ -121,7 +121,8 @@ static int read_las(icp_hip_ctx* c, const char* path, int rules, int64_t max_poi
   }
   icp_hip_ctx* m = worker(c);
   LasIo* io = nullptr;
-  int rc = hipSetDevice(m->device) == hipSuccess ? las_io(m, &io) : fail(ICP_HIP_EDEVICE, "hipSetDevice");
+  hipError_t e = hipSetDevice(m->device);
+  const int rc = e == hipSuccess ? las_io(m, &io) : fail_hip("hipSetDevice", e);
   if (rc != ICP_HIP_OK) {
     las_span_close(&sp);
     return rc;
@@ -132,7 +133,6 @@ static int read_las(icp_hip_ctx* c, const char* path, int rules, int64_t max_poi
     ax.offset[a] = sp.hdr.offset[a];
   }
   const int rl = sp.hdr.record_length;
-  hipError_t e = hipSuccess;
   bool short_file = false;
   for (int k = 0; e == hipSuccess; k++) {
     const int b = k & 1;
@@ -158,7 +158,7 @@ static int read_las(icp_hip_ctx* c, const char* path, int rules, int64_t max_poi
   const hipError_t es = hipStreamSynchronize(m->stream);
   if (e == hipSuccess) e = es;
   las_span_close(&sp);
-  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("LAS decode: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail_hip("LAS decode", e);
   if (short_file) return fail(ICP_HIP_EINVAL, std::string("LAS file changed while it was read: ") + path);
   *n_out = kept(sp.n, stride);
   c->las_device_path = 1;
@@ -196,15 +196,13 @@ static int write_las(icp_hip_ctx* c, const char* path, const double* d_xyz, int6
     }
   } else {
     const int64_t np = las_bounds_parts(n);
+    std::vector<double> parts(6 * (size_t)np);  // before its source's owner: outlives the copy
+    DevScratch S;
     double* d_parts = nullptr;
-    std::vector<double> parts(6 * (size_t)np);
-    hipError_t e = dalloc(&d_parts, parts.size());
-    if (e == hipSuccess) e = launch_las_bounds(d_xyz, n, d_parts, m->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(parts.data(), d_parts, parts.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    dfree(d_parts);
-    if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("LAS bounds: ") + hipGetErrorString(e));
+    HIP_TRY(S.alloc(&d_parts, parts.size()));
+    HIP_TRY(launch_las_bounds(d_xyz, n, d_parts, m->stream));
+    HIP_TRY(hipMemcpyAsync(parts.data(), d_parts, parts.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
     for (int a = 0; a < 3; a++) {
       if (flavour == ICP_LAS_CLI) {  // from points[0]: run 0 begins with it, and a repeat changes nothing
         mn[a] = parts[a];
@@ -226,13 +224,10 @@ static int write_las(icp_hip_ctx* c, const char* path, const double* d_xyz, int6
     ax.offset[a] = flavour == ICP_LAS_CLI ? offset[a] : mn[a];
   }
   unsigned long long bad = 0;
-  {
-    hipError_t e = hipMemsetAsync(io->count, 0, sizeof(unsigned long long), m->stream);
-    if (e == hipSuccess) e = launch_las_count_unencodable(d_xyz, n, ax, io->count, m->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, io->count, sizeof(bad), hipMemcpyDeviceToHost, m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("LAS encode check: ") + hipGetErrorString(e));
-  }
+  HIP_TRY(hipMemsetAsync(io->count, 0, sizeof(unsigned long long), m->stream));
+  HIP_TRY(launch_las_count_unencodable(d_xyz, n, ax, io->count, m->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, io->count, sizeof(bad), hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
   if (bad != 0) return write_fallback(c, path, d_xyz, n, flavour, scale, offset, bounds);
 
   std::FILE* f = std::fopen(path, "wb");
@@ -266,7 +261,7 @@ static int write_las(icp_hip_ctx* c, const char* path, const double* d_xyz, int6
   const hipError_t es = hipStreamSynchronize(m->stream);
   if (e == hipSuccess) e = es;
   ok = (std::fclose(f) == 0) && ok;
-  if (e != hipSuccess) return fail(ICP_HIP_EDEVICE, std::string("LAS encode: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail_hip("LAS encode", e);
   if (!ok) return fail(ICP_HIP_EINVAL, std::string("cannot write LAS file: ") + path);
   c->las_device_path = 1;
   return ICP_HIP_OK;
@@ -308,11 +303,11 @@ static int set_from_las(icp_hip_ctx* c, const char* path, int las_rules, int64_t
   void* d = nullptr;
   rc = icp_hip_dev_alloc(c, 3 * sizeof(double) * (size_t)(cap > 0 ? cap : 1), &d);
   if (rc != ICP_HIP_OK) return rc;
+  ScopeExit release([c, d] { (void)icp_hip_dev_free(c, d); });
   rc = read_las(c, path, las_rules, max_points, stride, static_cast<double*>(d), hdr, &n);
-  if (rc == ICP_HIP_OK)
-    rc = target ? icp_hip_set_target_device(c, static_cast<double*>(d), n, max_tree_points, max_depth, rules)
-                : icp_hip_set_source_device(c, static_cast<double*>(d), n);
-  (void)icp_hip_dev_free(c, d);
+  if (rc != ICP_HIP_OK) return rc;
+  rc = target ? icp_hip_set_target_device(c, static_cast<double*>(d), n, max_tree_points, max_depth, rules)
+              : icp_hip_set_source_device(c, static_cast<double*>(d), n);
   if (rc == ICP_HIP_OK && n_out) *n_out = n;
   return rc;
 }
@@ -335,10 +330,10 @@ int icp_hip_write_source_las(icp_hip_ctx* c, const char* path, int flavour, cons
   void* d = nullptr;
   int rc = icp_hip_dev_alloc(c, 3 * sizeof(double) * (size_t)n, &d);
   if (rc != ICP_HIP_OK) return rc;
+  ScopeExit release([c, d] { (void)icp_hip_dev_free(c, d); });
   rc = icp_hip_get_source_device(c, static_cast<double*>(d));
-  if (rc == ICP_HIP_OK) rc = write_las(c, path, static_cast<double*>(d), n, flavour, scale, offset, bounds);
-  (void)icp_hip_dev_free(c, d);
-  return rc;
+  if (rc != ICP_HIP_OK) return rc;
+  return write_las(c, path, static_cast<double*>(d), n, flavour, scale, offset, bounds);
 }
 
 int icp_hip_last_las_path(icp_hip_ctx* c, int32_t* device_path) {

@@ -22,12 +22,12 @@ namespace {
 // Queries per launch of the k-NN calls: bounds the scratch of the host variant (n x k outputs).
 constexpr int64_t kKnnSlice = (int64_t)1 << 22;
 
-int fail_hip(const char* what, hipError_t e) {
-  return fail(e == hipErrorOutOfMemory ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, std::string(what) + ": " + hipGetErrorString(e));
+int knn_k_check(int k) {
+  return k < 1 || k > ICP_HIP_KNN_MAX ? fail(ICP_HIP_EINVAL, "knn: k out of range [1, 32]") : ICP_HIP_OK;
 }
 
 int knn_check(const icp_hip_ctx* c, int k) {
-  if (k < 1 || k > ICP_HIP_KNN_MAX) return fail(ICP_HIP_EINVAL, "knn: k out of range [1, 32]");
+  if (const int rc = knn_k_check(k)) return rc;
   if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
   if ((int64_t)k > c->n_tgt) return fail(ICP_HIP_EINVAL, "knn: k exceeds the target size");
   return ICP_HIP_OK;
@@ -46,48 +46,40 @@ int knn_core(icp_hip_ctx* c, bool dev, const double* q, int64_t n, int k, int32_
     return ICP_HIP_OK;
   }
   const int64_t cap = std::min(n, kKnnSlice);
+  DevScratch S;
   double *dq = nullptr, *dd = nullptr;
   int32_t* di = nullptr;
-  hipError_t e = dalloc(&dq, 3 * (size_t)cap);
-  if (e == hipSuccess && idx_out) e = dalloc(&di, (size_t)cap * k);
-  if (e == hipSuccess && d2_out) e = dalloc(&dd, (size_t)cap * k);
-  for (int64_t off = 0; off < n && e == hipSuccess; off += kKnnSlice) {
+  HIP_TRY(S.alloc(&dq, 3 * (size_t)cap));
+  if (idx_out) HIP_TRY(S.alloc(&di, (size_t)cap * k));
+  if (d2_out) HIP_TRY(S.alloc(&dd, (size_t)cap * k));
+  for (int64_t off = 0; off < n; off += kKnnSlice) {
     const int64_t m = std::min(n - off, kKnnSlice);
-    e = hipMemcpyAsync(dq, q + 3 * off, 3 * sizeof(double) * m, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_knn(c->nodes, c->pts, c->levels, dq, m, k, di, dd, c->stream);
-    if (e == hipSuccess && idx_out)
-      e = hipMemcpyAsync(idx_out + off * k, di, sizeof(int32_t) * m * k, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && d2_out)
-      e = hipMemcpyAsync(d2_out + off * k, dd, sizeof(double) * m * k, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    HIP_TRY(hipMemcpyAsync(dq, q + 3 * off, 3 * sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_knn(c->nodes, c->pts, c->levels, dq, m, k, di, dd, c->stream));
+    if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out + off * k, di, sizeof(int32_t) * m * k, hipMemcpyDeviceToHost, c->stream));
+    if (d2_out) HIP_TRY(hipMemcpyAsync(d2_out + off * k, dd, sizeof(double) * m * k, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
   }
-  dfree(dq);
-  dfree(di);
-  dfree(dd);
-  if (e != hipSuccess) return fail_hip("knn", e);
   return ICP_HIP_OK;
 }
 
 // The caller's normals (device buffer, caller's target order) into the context, leaf order; the
 // context's normals are replaced only when every row is of unit length or zero.
 int set_normals_core(icp_hip_ctx* c, const double* d_aos) {
+  unsigned h_bad = 0;  // before its source's owner: outlives the copy
+  DevScratch S;
   double* leaf = nullptr;
   unsigned* bad = nullptr;
-  unsigned h_bad = 0;
-  hipError_t e = dalloc(&leaf, 3 * (size_t)c->n_tgt);
-  if (e == hipSuccess) e = dalloc(&bad, 1);
-  if (e == hipSuccess) e = hipMemsetAsync(bad, 0, sizeof(unsigned), c->stream);
-  if (e == hipSuccess) e = launch_normals_to_leaf(c->pts, d_aos, leaf, c->n_tgt, bad, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(bad);
-  if (e != hipSuccess || h_bad != 0) {
-    dfree(leaf);
-    if (e != hipSuccess) return fail_hip("set_target_normals", e);
+  HIP_TRY(S.alloc(&leaf, 3 * (size_t)c->n_tgt));
+  HIP_TRY(S.alloc(&bad, 1));
+  HIP_TRY(hipMemsetAsync(bad, 0, sizeof(unsigned), c->stream));
+  HIP_TRY(launch_normals_to_leaf(c->pts, d_aos, leaf, c->n_tgt, bad, c->stream));
+  HIP_TRY(hipMemcpyAsync(&h_bad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (h_bad != 0)
     return fail(ICP_HIP_EINVAL, "set_target_normals: " + std::to_string(h_bad) + " rows are neither of unit length nor zero");
-  }
   dfree(c->normals);
-  c->normals = leaf;
+  c->normals = S.keep(leaf);
   return ICP_HIP_OK;
 }
 
@@ -111,16 +103,16 @@ int icp_hip_knn_device(icp_hip_ctx* c, const double* d_q, int64_t n, int k, int3
   if (d_d2_out)
     if (const int rc = check_device_ptr(c, d_d2_out, "knn_device")) return rc;
   if (c->group) {  // the first member's replica, through host memory (the buffers may be another device's)
-    if (k < 1 || k > ICP_HIP_KNN_MAX) return fail(ICP_HIP_EINVAL, "knn: k out of range [1, 32]");
-    std::vector<double> hq(3 * (size_t)n);
+    if (const int rc = knn_k_check(k)) return rc;
+    std::vector<double> hq;
     std::vector<int32_t> idx(d_idx_out ? (size_t)n * k : 0);
     std::vector<double> d(d_d2_out ? (size_t)n * k : 0);
-    if (n > 0) HIP_TRY(hipMemcpy(hq.data(), d_q, hq.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(stage_down(c, &hq, d_q, 3 * (size_t)n));
     const int rc = icp_hip_knn(group_member(c, 0), hq.data(), n, k, d_idx_out ? idx.data() : nullptr,
                                d_d2_out ? d.data() : nullptr);
     if (rc != ICP_HIP_OK) return rc;
-    if (!idx.empty()) HIP_TRY(hipMemcpy(d_idx_out, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!d.empty()) HIP_TRY(hipMemcpy(d_d2_out, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(stage_up(c, d_idx_out, idx));
+    HIP_TRY(stage_up(c, d_d2_out, d));
     return ICP_HIP_OK;
   }
   if (const int rc = knn_check(c, k)) return rc;
@@ -138,17 +130,13 @@ int icp_hip_estimate_target_normals(icp_hip_ctx* c, int k, const double* viewpoi
     for (int a = 0; a < 3; a++)
       if (!(viewpoint[a] - viewpoint[a] == 0.0)) return fail(ICP_HIP_EINVAL, "estimate_target_normals: non-finite viewpoint");
   HIP_TRY(hipSetDevice(c->device));
+  DevScratch S;
   double* leaf = nullptr;
-  hipError_t e = dalloc(&leaf, 3 * (size_t)c->n_tgt);
-  if (e == hipSuccess)
-    e = launch_target_normals(c->nodes, c->pts, c->levels, c->n_tgt, k, viewpoint ? 1 : 0, viewpoint, leaf, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    dfree(leaf);
-    return fail_hip("estimate_target_normals", e);
-  }
+  HIP_TRY(S.alloc(&leaf, 3 * (size_t)c->n_tgt));
+  HIP_TRY(launch_target_normals(c->nodes, c->pts, c->levels, c->n_tgt, k, viewpoint ? 1 : 0, viewpoint, leaf, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   dfree(c->normals);
-  c->normals = leaf;
+  c->normals = S.keep(leaf);
   return ICP_HIP_OK;
 }
 
@@ -157,16 +145,11 @@ int icp_hip_set_target_normals(icp_hip_ctx* c, const double* n_xyz) {
   if (c->group) return icp_hip_set_target_normals(group_member(c, 0), n_xyz);
   if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
   HIP_TRY(hipSetDevice(c->device));
+  DevScratch S;
   double* up = nullptr;
-  hipError_t e = dalloc(&up, 3 * (size_t)c->n_tgt);
-  if (e == hipSuccess) e = hipMemcpyAsync(up, n_xyz, 3 * sizeof(double) * c->n_tgt, hipMemcpyHostToDevice, c->stream);
-  if (e != hipSuccess) {
-    dfree(up);
-    return fail_hip("set_target_normals", e);
-  }
-  const int rc = set_normals_core(c, up);
-  dfree(up);
-  return rc;
+  HIP_TRY(S.alloc(&up, 3 * (size_t)c->n_tgt));
+  HIP_TRY(hipMemcpyAsync(up, n_xyz, 3 * sizeof(double) * c->n_tgt, hipMemcpyHostToDevice, c->stream));
+  return set_normals_core(c, up);
 }
 
 int icp_hip_set_target_normals_device(icp_hip_ctx* c, const double* d_n_xyz) {
@@ -175,8 +158,8 @@ int icp_hip_set_target_normals_device(icp_hip_ctx* c, const double* d_n_xyz) {
   if (c->group) {
     icp_hip_ctx* m = group_member(c, 0);
     if (!m->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
-    std::vector<double> h(3 * (size_t)m->n_tgt);
-    HIP_TRY(hipMemcpy(h.data(), d_n_xyz, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<double> h;
+    HIP_TRY(stage_down(c, &h, d_n_xyz, 3 * (size_t)m->n_tgt));
     return icp_hip_set_target_normals(m, h.data());
   }
   if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
@@ -190,13 +173,12 @@ int icp_hip_get_target_normals(icp_hip_ctx* c, double* n_xyz_out) {
   if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
   if (!c->normals) return fail(ICP_HIP_ENOTREADY, "the target has no normals");
   HIP_TRY(hipSetDevice(c->device));
+  DevScratch S;
   double* aos = nullptr;
-  hipError_t e = dalloc(&aos, 3 * (size_t)c->n_tgt);
-  if (e == hipSuccess) e = launch_normals_from_leaf(c->pts, c->normals, aos, c->n_tgt, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(n_xyz_out, aos, 3 * sizeof(double) * c->n_tgt, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(aos);
-  if (e != hipSuccess) return fail_hip("get_target_normals", e);
+  HIP_TRY(S.alloc(&aos, 3 * (size_t)c->n_tgt));
+  HIP_TRY(launch_normals_from_leaf(c->pts, c->normals, aos, c->n_tgt, c->stream));
+  HIP_TRY(hipMemcpyAsync(n_xyz_out, aos, 3 * sizeof(double) * c->n_tgt, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return ICP_HIP_OK;
 }
 
@@ -208,7 +190,7 @@ int icp_hip_get_target_normals_device(icp_hip_ctx* c, double* d_n_xyz_out) {
     std::vector<double> h(3 * (size_t)m->n_tgt);
     const int rc = icp_hip_get_target_normals(m, h.data());
     if (rc != ICP_HIP_OK) return rc;
-    HIP_TRY(hipMemcpy(d_n_xyz_out, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(stage_up(c, d_n_xyz_out, h));
     return ICP_HIP_OK;
   }
   if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");

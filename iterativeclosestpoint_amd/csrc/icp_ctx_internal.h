@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <vector>
 
 #include "../../include/icp_hip.h"
 #include "ctx_util.h"
@@ -180,6 +181,25 @@ icp::NNLaunch base_launch(const icp_hip_ctx* c);
 // `what`) unless p is non-null, aligned, and device memory of the context's device or managed
 // memory by hipPointerGetAttributes. Never dereferences p.
 int check_device_ptr(const icp_hip_ctx* c, const void* p, const char* what, unsigned align = 8);
+
+// The host-staged routes of the device variants: the caller's buffer through host memory, complete
+// at return. A group's buffer may be any device's, so it is copied without the member's stream.
+template <typename T>
+hipError_t stage_down(const icp_hip_ctx* c, std::vector<T>* h, const T* d, size_t count) {
+  h->resize(count);
+  if (count == 0) return hipSuccess;
+  if (c->group) return hipMemcpy(h->data(), d, count * sizeof(T), hipMemcpyDeviceToHost);
+  hipError_t e = hipMemcpyAsync(h->data(), d, count * sizeof(T), hipMemcpyDeviceToHost, c->stream);
+  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
+
+template <typename T>
+hipError_t stage_up(const icp_hip_ctx* c, T* d, const std::vector<T>& h) {
+  if (h.empty()) return hipSuccess;
+  if (c->group) return hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+  hipError_t e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
+  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
 
 // --- ctx_prewalk.cpp
 // The prewalk's one safety rule: whatever frees, regenerates or reads the record buffers (wc_box,

@@ -198,6 +198,21 @@ int group_target_build_info(icp_hip_ctx* c, int32_t* on_device, double* build_ms
   return ICP_HIP_OK;
 }
 
+// The kd query order of the whole cloud, built on member m0's device into order[n].
+static hipError_t device_query_order(icp_hip_ctx* m0, const double* xyz, int64_t n, int32_t* order) {
+  hipError_t e = hipSetDevice(m0->device);
+  if (e != hipSuccess) return e;
+  DevScratch S;
+  double* d_xyz = nullptr;
+  int32_t* d_perm = nullptr;
+  if ((e = S.alloc(&d_xyz, 3 * (size_t)n)) != hipSuccess) return e;
+  if ((e = S.alloc(&d_perm, (size_t)n)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(d_xyz, xyz, 3 * sizeof(double) * (size_t)n, hipMemcpyHostToDevice, m0->stream)) != hipSuccess) return e;
+  if ((e = icp::gpu_kd_query_order(d_xyz, n, 8, d_perm, m0->stream)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(order, d_perm, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, m0->stream)) != hipSuccess) return e;
+  return hipStreamSynchronize(m0->stream);
+}
+
 int group_set_source(icp_hip_ctx* c, const double* xyz, int64_t n) {
   DeviceGroup* g = c->group;
   const int w = (int)g->members.size();
@@ -208,20 +223,7 @@ int group_set_source(icp_hip_ctx* c, const double* xyz, int64_t n) {
   g->order.assign((size_t)n, 0);
   bool ordered = false;
   if (c->cfg.query_order == 0) {
-    icp_hip_ctx* m0 = g->members[0];
-    double* d_xyz = nullptr;
-    int32_t* d_perm = nullptr;
-    hipError_t e = hipSetDevice(m0->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_xyz), 3 * sizeof(double) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_perm), sizeof(int32_t) * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_xyz, xyz, 3 * sizeof(double) * (size_t)n, hipMemcpyHostToDevice, m0->stream);
-    if (e == hipSuccess) e = icp::gpu_kd_query_order(d_xyz, n, 8, d_perm, m0->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(g->order.data(), d_perm, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, m0->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m0->stream);
-    if (d_xyz) (void)hipFree(d_xyz);
-    if (d_perm) (void)hipFree(d_perm);
-    ordered = e == hipSuccess;
+    ordered = device_query_order(g->members[0], xyz, n, g->order.data()) == hipSuccess;
     if (!ordered) (void)hipGetLastError();
   }
   if (!ordered) icp::kd_query_order(xyz, n, 8, &g->order);

@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_scratch.h"
 #include "octree_gpu.h"
 
 namespace icp {
@@ -333,21 +334,6 @@ __global__ void k_total(const int64_t* __restrict__ excl, const int64_t* __restr
   *out = excl[n - 1] + last_in[n - 1];
 }
 
-// Scratch arrays, freed on every exit path.
-struct Scratch {
-  std::vector<void*> ptrs;
-  ~Scratch() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <typename T>
-  hipError_t alloc(T** p, size_t count) {
-    *p = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) ptrs.push_back(*p);
-    return e;
-  }
-};
-
 // Cell table of level L: entry e (an L-level path prefix, level 1 in the top 3 bits) = the
 // node holding every target point of that cell: the node at depth L, or the leaf above it, as
 // (node id << 5) | node depth; -1 when the cell holds no point (a child on the path is absent).
@@ -424,7 +410,7 @@ int gpu_build_octree(const double* xyz, int64_t n, int max_pts, int max_d, hipSt
     return 1;
   }
   const int64_t m = max_pts > 0 ? max_pts : 0;  // count <= max_pts with max_pts < 0 never holds
-  Scratch S;
+  DevScratch S;  // the scratch arrays, and the tree until it is handed over
 
   // 1. root box
   const int nbb = (int)std::min<int64_t>(1024, grid_for(n, kTB));
@@ -583,9 +569,8 @@ int gpu_build_octree(const double* xyz, int64_t n, int max_pts, int max_d, hipSt
 
   NodeRec* nodes = nullptr;
   TgtPt* pts = nullptr;
-  OCT_TRY(hipMalloc(reinterpret_cast<void**>(&nodes), nn * sizeof(NodeRec)));
-  if (hipMalloc(reinterpret_cast<void**>(&pts), n * sizeof(TgtPt)) != hipSuccess) {
-    (void)hipFree(nodes);
+  OCT_TRY(S.alloc(&nodes, nn));
+  if (S.alloc(&pts, n) != hipSuccess) {
     *why = "allocating the leaf-ordered target failed";
     return -2;
   }
@@ -595,13 +580,11 @@ int gpu_build_octree(const double* xyz, int64_t n, int max_pts, int max_d, hipSt
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
-    (void)hipFree(nodes);
-    (void)hipFree(pts);
     *why = std::string("octree build kernels: ") + hipGetErrorString(e);
     return -3;
   }
-  out->nodes = nodes;
-  out->pts = pts;
+  out->nodes = S.keep(nodes);
+  out->pts = S.keep(pts);
   out->n_nodes = nn;
   out->n_leaves = nleaves;
   out->max_depth = (int32_t)maxdep;

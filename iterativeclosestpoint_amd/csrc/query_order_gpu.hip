@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_scratch.h"
 #include "query_order.h"
 
 namespace icp {
@@ -176,13 +177,10 @@ inline int64_t split_at(int64_t n, int bucket) {
   return h;
 }
 
-#define QO_TRY(expr)                     \
-  do {                                   \
-    hipError_t e_ = (expr);              \
-    if (e_ != hipSuccess) {              \
-      err = e_;                          \
-      goto done;                         \
-    }                                    \
+#define QO_TRY(expr)                  \
+  do {                                \
+    hipError_t e_ = (expr);           \
+    if (e_ != hipSuccess) return e_;  \
   } while (0)
 
 }  // namespace
@@ -221,28 +219,28 @@ hipError_t gpu_kd_query_order(const double* d_xyz, int64_t n, int bucket, int32_
       sz.swap(sz2);
     }
   }
-  hipError_t err = hipSuccess;
   size_t max_seg = 0;
   for (const auto& v : lv_start) max_seg = std::max(max_seg, v.size());
+  DevScratch S;  // every level ends synchronised; a failed one leaves the wait to the release
   int32_t *d_starts = nullptr, *d_sizes = nullptr, *perm_alt = nullptr;
   uint8_t* d_axis = nullptr;
   uint64_t *keys = nullptr, *keys_alt = nullptr;
-  void* d_chunks = nullptr;  // chunk boxes + chunk / big-segment tables
+  uint8_t* d_chunks = nullptr;  // chunk boxes + chunk / big-segment tables
   size_t chunk_cap = 0;
-  void* tmp = nullptr;
+  uint8_t* tmp = nullptr;
   size_t tmp_bytes = 0;
   int sbits = 1;
   while (((int64_t)1 << sbits) <= n) sbits++;
   const int end_bit = 32 + sbits;
-  QO_TRY(hipMalloc(reinterpret_cast<void**>(&d_starts), max_seg * sizeof(int32_t)));
-  QO_TRY(hipMalloc(reinterpret_cast<void**>(&d_sizes), max_seg * sizeof(int32_t)));
-  QO_TRY(hipMalloc(reinterpret_cast<void**>(&d_axis), max_seg));
-  QO_TRY(hipMalloc(reinterpret_cast<void**>(&perm_alt), (size_t)n * sizeof(int32_t)));
-  QO_TRY(hipMalloc(reinterpret_cast<void**>(&keys), (size_t)n * sizeof(uint64_t)));
-  QO_TRY(hipMalloc(reinterpret_cast<void**>(&keys_alt), (size_t)n * sizeof(uint64_t)));
+  QO_TRY(S.alloc(&d_starts, max_seg));
+  QO_TRY(S.alloc(&d_sizes, max_seg));
+  QO_TRY(S.alloc(&d_axis, max_seg));
+  QO_TRY(S.alloc(&perm_alt, (size_t)n));
+  QO_TRY(S.alloc(&keys, (size_t)n));
+  QO_TRY(S.alloc(&keys_alt, (size_t)n));
   QO_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_alt, d_perm, perm_alt, (int)n, 0,
                                             end_bit, s));
-  QO_TRY(hipMalloc(&tmp, tmp_bytes));
+  QO_TRY(S.alloc(&tmp, tmp_bytes));
   for (size_t L = 0; L < lv_start.size(); L++) {
     const int nseg = (int)lv_start[L].size();
     QO_TRY(hipMemcpyAsync(d_starts, lv_start[L].data(), nseg * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -262,11 +260,8 @@ hipError_t gpu_kd_query_order(const double* d_xyz, int64_t n, int bucket, int32_
       if (!bseg.empty()) {
         const size_t nc = cst.size(), nb = bseg.size();
         if (nc > chunk_cap) {
-          if (d_chunks) (void)hipFree(d_chunks);
-          d_chunks = nullptr;
           chunk_cap = nc;
-          QO_TRY(hipMalloc(reinterpret_cast<void**>(&d_chunks), chunk_cap * (6 * sizeof(float) + 3 * sizeof(int32_t)) +
-                                                                 2 * sizeof(int32_t)));
+          QO_TRY(S.regrow(&d_chunks, chunk_cap * (6 * sizeof(float) + 3 * sizeof(int32_t)) + 2 * sizeof(int32_t)));
         }
         float* cbox = reinterpret_cast<float*>(d_chunks);
         int32_t* ci = reinterpret_cast<int32_t*>(cbox + 6 * chunk_cap);
@@ -295,12 +290,7 @@ hipError_t gpu_kd_query_order(const double* d_xyz, int64_t n, int bucket, int32_
     // the host tables of this level are read by the copies above: finish before they are reused
     QO_TRY(hipStreamSynchronize(s));
   }
-done:
-  (void)hipStreamSynchronize(s);
-  for (void* p : {(void*)d_starts, (void*)d_sizes, (void*)d_axis, (void*)perm_alt, (void*)keys, (void*)keys_alt, tmp,
-                  d_chunks})
-    if (p) (void)hipFree(p);
-  return err;
+  return hipSuccess;
 }
 
 }  // namespace icp

@@ -247,6 +247,11 @@ def test_rejected_arguments_leave_the_context_usable(icp):
             ctx.set_target_device(d_bad, n_t)
         assert e_dev.value.code == e_host.value.code == icp.EINVAL
         assert str(e_dev.value) == str(e_host.value)
+        # without a target as a whole: no nodes, and no build to report
+        assert ctx.target_info()["n_nodes"] == 0
+        with pytest.raises(icp.IcpError) as e_info:
+            ctx.target_build_info()
+        assert e_info.value.code == icp.ENOTREADY
         with pytest.raises(icp.IcpError) as e_it:
             ctx.iterate(None, 0, icp.RULES_ENGINE, 3.0)
         assert e_it.value.code == icp.ENOTREADY
