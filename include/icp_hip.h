@@ -365,16 +365,31 @@ int icp_hip_target_build_info(icp_hip_ctx* ctx, int32_t* on_device, double* buil
 int icp_hip_copy_target(icp_hip_ctx* ctx, double* box6, int32_t* first, uint32_t* meta, int32_t* depth,
                         double* xyz, int32_t* orig);
 
+/* The structures the searches derive from the resident octree (inspection / tests, as
+ * icp_hip_copy_target; a device group answers for its first member). tbox6: n_nodes x 6 floats, the
+ * tight box of every node, lo then hi (the bounding box of the target points below it, rounded
+ * outwards to fp32). cells: the per-level cell tables, (8^(lmax + 1) - 1) / 7 ints, level l at
+ * offset (8^l - 1) / 7, entry = (node << 5) | depth of the node that holds the cell's points, -1 for
+ * an empty cell; cells_cap is the capacity of `cells` in ints (ICP_HIP_EINVAL when too small).
+ * *cell_lmax: the deepest table level, -1 when the context has no tables (config cell_starts = 0).
+ * Null pointers skip a part. */
+int icp_hip_copy_target_aux(icp_hip_ctx* ctx, float* tbox6, int32_t* cells, int64_t cells_cap, int32_t* cell_lmax);
+
 /* The separation of every target point (caller's target order): a lower bound of its distance
  * to every other target point, 0 when it has an exact duplicate (computed by set_target when
  * config certify_prev != 0; zeros otherwise). Inspection / tests. */
 int icp_hip_target_separation(icp_hip_ctx* ctx, float* sep_out);
 
-/* Upload this rank's source shard (AoS xyz). Queries are reordered on the device along a
- * Morton curve for traversal coherence; every output is returned in the caller's order.
+/* Upload this rank's source shard (AoS xyz). Queries are reordered into kd buckets of 64 (one wave;
+ * config query_order, icp_hip_copy_query_order); every output is returned in the caller's order.
  * A shard holds fewer than 2^29 points (ICP_HIP_EINVAL otherwise; shard larger clouds over a
  * device group). Whole or not at all, as icp_hip_set_target. */
 int icp_hip_set_source(icp_hip_ctx* ctx, const double* xyz, int64_t n);
+
+/* The installed query order of the source (inspection / tests): perm_out[k] = the caller's index
+ * of the query stored at slot k, source size ints. A device group returns the order of the whole
+ * cloud, whose contiguous ranges are its members' shards. ICP_HIP_ENOTREADY without a source. */
+int icp_hip_copy_query_order(icp_hip_ctx* ctx, int32_t* perm_out);
 
 /* One ICP iteration body. If T_apply (row-major 4x4) is non-null, src = T_apply * src is applied
  * first (fused into the search kernel). `iter` and `rules` select the threshold rule,

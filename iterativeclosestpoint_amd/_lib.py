@@ -210,6 +210,8 @@ SIGNATURES = {
     "icp_hip_target_build_info": (C.c_int, [_P, _I32, _D]),
     "icp_hip_copy_target": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "icp_hip_target_separation": (C.c_int, [_P, _P]),
+    "icp_hip_copy_target_aux": (C.c_int, [_P, _P, _P, C.c_int64, _I32]),
+    "icp_hip_copy_query_order": (C.c_int, [_P, _P]),
     "icp_hip_set_prewalk": (C.c_int, [_P, C.c_double]),
     "icp_hip_synchronize": (C.c_int, [_P]),
     "icp_hip_comm_abort": (C.c_int, [_P]),
@@ -626,6 +628,23 @@ class Context:
         out = np.empty(self._n_tgt, np.float32)
         _check(lib().icp_hip_target_separation(self._h, _ptr(out)))
         return out
+
+    def copy_target_aux(self) -> dict:
+        """The searches' derived target structures (icp_hip_copy_target_aux): "tbox" (n_nodes, 6)
+        float32, lo then hi; "cell_lmax" (-1: no tables); "cells", the tables of levels
+        0..cell_lmax back to back (level l at offset (8^l - 1) / 7), empty without tables."""
+        lmax = C.c_int32()
+        _check(lib().icp_hip_copy_target_aux(self._h, None, None, 0, C.byref(lmax)))
+        tbox = np.empty((self.target_info()["n_nodes"], 6), np.float32)
+        cells = np.empty((8 ** (lmax.value + 1) - 1) // 7 if lmax.value >= 0 else 0, np.int32)
+        _check(lib().icp_hip_copy_target_aux(self._h, _ptr(tbox), _ptr(cells), cells.shape[0], C.byref(lmax)))
+        return {"tbox": tbox, "cells": cells, "cell_lmax": lmax.value}
+
+    def query_order(self) -> np.ndarray:
+        """The installed query order (icp_hip_copy_query_order): slot k holds caller index out[k]."""
+        out = np.empty(max(1, self.n_src), np.int32)
+        _check(lib().icp_hip_copy_query_order(self._h, _ptr(out)))
+        return out[: self.n_src]
 
     def last_timing(self):
         a, b = C.c_double(), C.c_double()

@@ -85,6 +85,7 @@ static void keep_tree_info(icp_hip_ctx* c, const Tree& t, int64_t n_nodes) {
   c->n_leaves = t.n_leaves;
   c->pos0 = t.pos_of_orig0;
   c->max_depth = t.max_depth;
+  c->max_inner_depth = t.max_inner_depth;
   c->levels = t.max_inner_depth + 1 > 0 ? t.max_inner_depth + 1 : 1;
 }
 
@@ -172,7 +173,7 @@ static int set_target_core(icp_hip_ctx* c, const double* xyz, const double* d_in
     }
   }
   if (c->cfg.cell_starts && c->n_nodes < ((int64_t)1 << 26)) {
-    const int lmax = cell_table_depth(c->n_leaves, c->levels - 1);
+    const int lmax = cell_table_depth(c->n_leaves, c->max_inner_depth);  // a root leaf: level 0 alone
     // the tables only speed up the searches' start: without memory for them the searches start
     // from the root (identical results)
     if (dalloc(&c->cells, (size_t)cell_table_entries(lmax)) == hipSuccess) {
@@ -311,6 +312,28 @@ int icp_hip_target_separation(icp_hip_ctx* c, float* sep_out) {
   return ICP_HIP_OK;
 }
 
+int icp_hip_copy_target_aux(icp_hip_ctx* c, float* tbox6, int32_t* cells, int64_t cells_cap, int32_t* cell_lmax) {
+  if (!c) return fail(ICP_HIP_EINVAL, "null context");
+  if (c->group) return icp_hip_copy_target_aux(group_member(c, 0), tbox6, cells, cells_cap, cell_lmax);
+  if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
+  const int lmax = c->cells ? c->cell_lmax : -1;
+  const int64_t nent = lmax >= 0 ? cell_table_entries(lmax) : 0;
+  if (cells && cells_cap < nent) return fail(ICP_HIP_EINVAL, "copy_target_aux: cells_cap smaller than the cell tables");
+  if (cell_lmax) *cell_lmax = lmax;
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<TBox> tb(tbox6 ? (size_t)c->n_nodes : 0);
+  if (tbox6) HIP_TRY(hipMemcpyAsync(tb.data(), c->tbox, tb.size() * sizeof(TBox), hipMemcpyDeviceToHost, c->stream));
+  if (cells && nent > 0)
+    HIP_TRY(hipMemcpyAsync(cells, c->cells, (size_t)nent * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < tb.size(); i++)
+    for (int k = 0; k < 3; k++) {
+      tbox6[6 * i + k] = tb[i].lo[k];
+      tbox6[6 * i + 3 + k] = tb[i].hi[k];
+    }
+  return ICP_HIP_OK;
+}
+
 int icp_hip_target_info(icp_hip_ctx* c, int64_t* n_nodes, int64_t* n_leaves, int32_t* max_depth, int32_t* levels) {
   if (!c) return fail(ICP_HIP_EINVAL, "null ctx");
   if (c->group) return icp_hip_target_info(group_member(c, 0), n_nodes, n_leaves, max_depth, levels);
@@ -412,6 +435,16 @@ int icp_hip_set_source_device(icp_hip_ctx* c, const double* d_xyz, int64_t n) {
     return group_set_source(c, staged.data(), n);
   }
   return set_source_core(c, nullptr, d_xyz, n);
+}
+
+int icp_hip_copy_query_order(icp_hip_ctx* c, int32_t* perm_out) {
+  if (!c || !perm_out) return fail(ICP_HIP_EINVAL, "null argument");
+  if (c->group) return group_copy_query_order(c, perm_out);
+  if (c->n_src == 0 || !c->perm) return fail(ICP_HIP_ENOTREADY, "source not set");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(perm_out, c->perm, sizeof(int32_t) * c->n_src, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ICP_HIP_OK;
 }
 
 int icp_hip_apply(icp_hip_ctx* c, const double* T) {

@@ -96,6 +96,7 @@ struct icp_hip_ctx {
   icp::TgtPt* pts = nullptr;
   int64_t n_nodes = 0, n_leaves = 0, n_tgt = 0;
   int32_t pos0 = 0, max_depth = -1, levels = 1;
+  int32_t max_inner_depth = -1;  // depth of the deepest inner node (-1: the root is a leaf)
   double init_best = 1.7976931348623157e308;
   int32_t* cells = nullptr;     // per-level cell tables of the octree (octree_gpu.h)
   int cell_lmax = -1;
@@ -260,6 +261,7 @@ int group_target_build_info(icp_hip_ctx* c, int32_t* on_device, double* build_ms
 int group_set_source(icp_hip_ctx* c, const double* xyz, int64_t n);
 int group_iterate(icp_hip_ctx* c, const double* T_apply, int iter, int rules, double sigma, icp_iter_stats* out);
 int group_apply(icp_hip_ctx* c, const double* T);
+int group_copy_query_order(icp_hip_ctx* c, int32_t* perm_out);
 int group_get_source(icp_hip_ctx* c, double* xyz_out);
 int group_get_correspondences(icp_hip_ctx* c, int32_t* idx_out, double* dist_out);
 int group_traversal_counts(icp_hip_ctx* c, double* mean_entries, double* mean_points);

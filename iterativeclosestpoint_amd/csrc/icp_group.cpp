@@ -237,6 +237,13 @@ int group_set_source(icp_hip_ctx* c, const double* xyz, int64_t n) {
   });
 }
 
+int group_copy_query_order(icp_hip_ctx* c, int32_t* perm_out) {
+  const DeviceGroup* g = c->group;
+  if (g->n_src == 0) return fail(ICP_HIP_ENOTREADY, "source not set");
+  std::memcpy(perm_out, g->order.data(), sizeof(int32_t) * (size_t)g->n_src);
+  return ICP_HIP_OK;
+}
+
 int group_iterate(icp_hip_ctx* c, const double* T_apply, int iter, int rules, double sigma, icp_iter_stats* out) {
   DeviceGroup* g = c->group;
   const int w = (int)g->members.size();

@@ -1,22 +1,43 @@
 // query_order_gpu.hip — the kd query order of query_order.cpp, built on the device.
 //
 // The host partition splits a range of n > bucket queries at h = n/2 rounded up to a multiple of
-// 64 (of `bucket` inside a wave's 64), on the longest axis of the range's bounding box, with
-// nth_element. The split positions depend on the sizes only, so every level of the recursion is a
-// fixed list of segments: the host lays the segments out level by level, and per level the device
-//   1. takes each splitting segment's bounding box (one workgroup per segment, fp32: the axis
-//      choice needs no exact extent) and picks its longest axis;
-//   2. keys every query with (segment start << 32 | order-preserving fp32 key of its coordinate on
-//      the segment's axis) and radix-sorts the permutation by it (hipCUB, stable): every
-//      segment ends up sorted along its axis, so its first h queries are its h smallest, which is
-//      what nth_element guarantees.
-// Finished segments (size <= bucket) keep their place (their start is their key). ~20 levels at
-// 10M. Any kd partition gives the same correspondences (the search is exact); this one has the
-// host order's bucket geometry. Non-finite coordinates count as 0, as on the host.
+// 64 (of `bucket` inside a wave's 64; h = n - unit when that reaches n), on the longest axis of the
+// range's bounding box, with nth_element. The split positions depend on the sizes only, so every
+// level of the recursion is a fixed list of segments: the host lays the segments out level by
+// level (a level holds every segment, in position order; the last level is the last one in which a
+// segment still splits).
+//
+// Coordinates. Keys and boxes are fp32, but of the coordinate relative to one origin per cloud:
+//   c(v, a) = (float)((finite(v) ? v : 0.0) - origin[a]) + 0.0f,   the subtraction in fp64,
+// so that a georeferenced cloud (|v| ~ 5e6, fp32 ulp 0.5 m) keeps the resolution of its extent. A
+// non-finite coordinate counts as 0, as on the host. The + 0.0f makes a zero +0.0: coordinates
+// that compare equal (-0.0 and +0.0) get one key, as they tie on the host. The origin is taken
+// once, before the first level, from a strided sample: stride = ceil(n / 1024), the points 0,
+// stride, 2 stride, ... (at most 1024 of them); per axis the finite sample values sorted ascending,
+// origin[a] = the value at index count / 2, or 0.0 when no sample value is finite (the sign of a
+// zero origin does not reach c). A median, not a box corner or a mean:
+// a few far outliers in the cloud (or in a segment) do not move it, and the bulk keeps its
+// resolution. The origin is per cloud, not per segment.
+//
+// Per level the device
+//   1. takes each splitting segment's bounding box over c (one workgroup per segment; segments
+//      larger than kChunk slots from chunk boxes: min and max are exact, so the route does not
+//      show) and picks its longest axis: extent hi - lo in fp32, the largest wins, ties go to the
+//      lower axis (the host's strict > scan);
+//   2. keys every slot with (segment start << 32 | k), k = the order-preserving image of the bits
+//      of c on the segment's axis (sign bit set: all bits flipped, else the sign bit set), and
+//      radix-sorts the permutation by it (hipCUB, stable): every segment
+//      ends up sorted along its axis, ties in the order the previous level left, so its first h
+//      queries are its h smallest, which is what nth_element guarantees.
+// Finished segments (size <= bucket) keep their place and their order: their key is their start
+// alone (k = 0). The first level starts from the identity. ~20 levels at 10M. Any kd partition
+// gives the same correspondences (the search is exact); this one has the host order's bucket
+// geometry.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -28,7 +49,24 @@ namespace icp {
 
 namespace {
 
-__device__ __forceinline__ float coord32(double v) { return __builtin_isfinite(v) ? (float)v : 0.0f; }
+struct Origin {
+  double o[3];
+};
+
+// the fp32 coordinate relative to the cloud's origin (non-finite: 0; a zero result: +0.0)
+__device__ __forceinline__ float coord32(double v, double o) {
+  return (float)((__builtin_isfinite(v) ? v : 0.0) - o) + 0.0f;
+}
+
+constexpr int kOriginSample = 1024;
+constexpr uint8_t kNoAxis = 3;  // a finished segment: no key
+
+// The strided sample the origin is the median of.
+__global__ void k_sample(const double* __restrict__ xyz, int64_t stride, int m, double* __restrict__ out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= m) return;
+  for (int a = 0; a < 3; a++) out[3 * k + a] = xyz[3 * (k * stride) + a];
+}
 
 __device__ __forceinline__ uint32_t okey(float f) {  // order-preserving (non-NaN floats)
   const uint32_t b = __float_as_uint(f);
@@ -78,7 +116,7 @@ __device__ __forceinline__ uint8_t longest_axis(const float lo[3], const float h
 // Big segments: the box of each chunk of kChunk slots (one workgroup each) ...
 __global__ void __launch_bounds__(256) k_chunk_bbox(const double* __restrict__ xyz, const int32_t* __restrict__ perm,
                                                     const int32_t* __restrict__ cstart, const int32_t* __restrict__ clen,
-                                                    float* __restrict__ cbox) {
+                                                    Origin og, float* __restrict__ cbox) {
   __shared__ float red[6][4];
   const int c = blockIdx.x;
   const int32_t s0 = cstart[c], n = clen[c];
@@ -88,7 +126,7 @@ __global__ void __launch_bounds__(256) k_chunk_bbox(const double* __restrict__ x
     const int64_t j = perm[s0 + k];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-      const float v = coord32(xyz[3 * j + a]);
+      const float v = coord32(xyz[3 * j + a], og.o[a]);
       lo[a] = v < lo[a] ? v : lo[a];
       hi[a] = v > hi[a] ? v : hi[a];
     }
@@ -120,14 +158,14 @@ __global__ void k_big_axis(const float* __restrict__ cbox, const int32_t* __rest
 // host's strict > scan).
 __global__ void __launch_bounds__(256) k_seg_axis(const double* __restrict__ xyz, const int32_t* __restrict__ perm,
                                                   const int32_t* __restrict__ starts,
-                                                  const int32_t* __restrict__ sizes, int bucket,
+                                                  const int32_t* __restrict__ sizes, int bucket, Origin og,
                                                   uint8_t* __restrict__ axis) {
   __shared__ float red[6][4];
   const int seg = blockIdx.x;
   const int32_t s0 = starts[seg], sz = sizes[seg];
   if (sz > kChunk) return;  // a big segment: the chunk path (k_chunk_bbox, k_big_axis)
   if (sz <= bucket) {  // finished: never split again
-    if (threadIdx.x == 0) axis[seg] = 0;
+    if (threadIdx.x == 0) axis[seg] = kNoAxis;
     return;
   }
   float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
@@ -136,7 +174,7 @@ __global__ void __launch_bounds__(256) k_seg_axis(const double* __restrict__ xyz
     const int64_t j = perm[s0 + k];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-      const float v = coord32(xyz[3 * j + a]);
+      const float v = coord32(xyz[3 * j + a], og.o[a]);
       lo[a] = v < lo[a] ? v : lo[a];
       hi[a] = v > hi[a] ? v : hi[a];
     }
@@ -145,10 +183,11 @@ __global__ void __launch_bounds__(256) k_seg_axis(const double* __restrict__ xyz
   if (threadIdx.x == 0) axis[seg] = longest_axis(lo, hi);
 }
 
-// Sort key of every slot: its segment's start (high word) and its coordinate on that segment's axis.
+// Sort key of every slot: its segment's start (high word) and its coordinate on that segment's axis
+// (a finished segment: the start alone).
 __global__ void k_seg_keys(const double* __restrict__ xyz, const int32_t* __restrict__ perm,
                            const int32_t* __restrict__ starts, int nseg, const uint8_t* __restrict__ axis,
-                           int64_t n, uint64_t* __restrict__ keys) {
+                           Origin og, int64_t n, uint64_t* __restrict__ keys) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   int lo = 0, hi = nseg;  // the last segment with start <= k
@@ -157,8 +196,13 @@ __global__ void k_seg_keys(const double* __restrict__ xyz, const int32_t* __rest
     if (starts[mid] <= k) lo = mid;
     else hi = mid;
   }
-  const int64_t j = perm[k];
-  keys[k] = ((uint64_t)(uint32_t)starts[lo] << 32) | okey(coord32(xyz[3 * j + axis[lo]]));
+  const int ax = axis[lo];
+  uint32_t low = 0;
+  if (ax != kNoAxis) {
+    const int64_t j = perm[k];
+    low = okey(coord32(xyz[3 * j + ax], og.o[ax]));
+  }
+  keys[k] = ((uint64_t)(uint32_t)starts[lo] << 32) | low;
 }
 
 __global__ void k_iota(int32_t* p, int64_t n) {
@@ -182,6 +226,28 @@ inline int64_t split_at(int64_t n, int bucket) {
     hipError_t e_ = (expr);           \
     if (e_ != hipSuccess) return e_;  \
   } while (0)
+
+// The cloud's origin (header comment): per axis the median of the finite coordinates of a strided
+// sample of at most kOriginSample points. d_sample: 3 * kOriginSample doubles. Synchronises s.
+hipError_t cloud_origin(const double* d_xyz, int64_t n, double* d_sample, hipStream_t s, Origin* og) {
+  const int64_t stride = (n + kOriginSample - 1) / kOriginSample;
+  const int m = (int)((n + stride - 1) / stride);
+  std::vector<double> h(3 * (size_t)m);
+  hipLaunchKernelGGL(k_sample, dim3(grid_for(m, 256)), dim3(256), 0, s, d_xyz, stride, m, d_sample);
+  QO_TRY(hipGetLastError());
+  QO_TRY(hipMemcpyAsync(h.data(), d_sample, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  QO_TRY(hipStreamSynchronize(s));
+  std::vector<double> v;
+  v.reserve((size_t)m);
+  for (int a = 0; a < 3; a++) {
+    v.clear();
+    for (int k = 0; k < m; k++)
+      if (std::isfinite(h[3 * (size_t)k + a])) v.push_back(h[3 * (size_t)k + a]);
+    std::sort(v.begin(), v.end());
+    og->o[a] = v.empty() ? 0.0 : v[v.size() / 2];
+  }
+  return hipSuccess;
+}
 
 }  // namespace
 
@@ -241,6 +307,10 @@ hipError_t gpu_kd_query_order(const double* d_xyz, int64_t n, int bucket, int32_
   QO_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_alt, d_perm, perm_alt, (int)n, 0,
                                             end_bit, s));
   QO_TRY(S.alloc(&tmp, tmp_bytes));
+  double* d_sample = nullptr;
+  QO_TRY(S.alloc(&d_sample, 3 * (size_t)kOriginSample));
+  Origin og;
+  QO_TRY(cloud_origin(d_xyz, n, d_sample, s, &og));
   for (size_t L = 0; L < lv_start.size(); L++) {
     const int nseg = (int)lv_start[L].size();
     QO_TRY(hipMemcpyAsync(d_starts, lv_start[L].data(), nseg * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -270,7 +340,7 @@ hipError_t gpu_kd_query_order(const double* d_xyz, int64_t n, int bucket, int32_
         QO_TRY(hipMemcpyAsync(ci + 2 * chunk_cap, bseg.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice, s));
         QO_TRY(hipMemcpyAsync(ci + 2 * chunk_cap + nb, bfirst.data(), (nb + 1) * sizeof(int32_t),
                               hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_chunk_bbox, dim3((unsigned)nc), dim3(256), 0, s, d_xyz, d_perm, ci, ci + chunk_cap, cbox);
+        hipLaunchKernelGGL(k_chunk_bbox, dim3((unsigned)nc), dim3(256), 0, s, d_xyz, d_perm, ci, ci + chunk_cap, og, cbox);
         hipLaunchKernelGGL(k_big_axis, dim3(grid_for((int64_t)nb, 64)), dim3(64), 0, s, cbox, ci + 2 * chunk_cap,
                            ci + 2 * chunk_cap + nb, (int)nb, d_axis);
         QO_TRY(hipGetLastError());
@@ -280,9 +350,9 @@ hipError_t gpu_kd_query_order(const double* d_xyz, int64_t n, int bucket, int32_
     const int32_t big = *std::max_element(lv_size[L].begin(), lv_size[L].end());
     const int bs = big <= 128 ? 64 : 256;  // deep levels: one wave per (small) segment
     hipLaunchKernelGGL(k_seg_axis, dim3((unsigned)nseg), dim3(bs), 0, s, d_xyz, d_perm, d_starts, d_sizes, bucket,
-                       d_axis);
-    hipLaunchKernelGGL(k_seg_keys, dim3(grid_for(n, 256)), dim3(256), 0, s, d_xyz, d_perm, d_starts, nseg, d_axis, n,
-                       keys);
+                       og, d_axis);
+    hipLaunchKernelGGL(k_seg_keys, dim3(grid_for(n, 256)), dim3(256), 0, s, d_xyz, d_perm, d_starts, nseg, d_axis, og,
+                       n, keys);
     QO_TRY(hipGetLastError());
     QO_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_alt, d_perm, perm_alt, (int)n, 0, end_bit,
                                               s));

@@ -103,7 +103,8 @@ def test_wide_pass_modes_agree(icp, oracle, scene, which):
     overflowed wave's box in segments) against the ball search taking those queries: the same
     correspondences, residuals and statistics bit for bit over 4 iterates (every iterate's
     correspondences checked against the oracle with the pass always on), also without the half
-    pass of the first iterate."""
+    pass of the first iterate. And the rule inside the device-resident loop (device_loop = 1), where
+    the overflow count that decides the next iterate's pass has to come back with the batch."""
     if which == "scene":
         tgt, src, _ = scene
     else:
@@ -132,6 +133,30 @@ def test_wide_pass_modes_agree(icp, oracle, scene, which):
         for (i0, d0), (i1, d1) in zip(out[key][1], out[(1, 1)][1]):
             np.testing.assert_array_equal(i0, i1)
             np.testing.assert_array_equal(d0, d1)
+    # The rule (wide_pass = 0) inside the device-resident loop, one iterate per batch: the count of
+    # overflowed waves that decides the next iterate's pass comes back from the device with the
+    # batch's record (FollowBuffers::last_wide). After an iterate that overflowed at least
+    # max(256, waves / 32) waves, the next one runs the wide pass.
+    with icp.Context(0, icp.config(wide_pass=0, device_loop=1, debug_counters=1)) as ctx:
+        ctx.set_target(tgt, 10, 20, icp.RULES_ENGINE)
+        ctx.set_source(src)
+        sess = ctx.session(icp.params_default(max_iterations=4, tolerance=0.0))
+        counters = []
+        for it in range(4):
+            assert sess.step_n(1) == 1
+            counters.append(ctx.debug_counters())
+            if it == 0:  # the same queries: the same answers as the host-driven iterates
+                idx, d = ctx.get_correspondences()
+                np.testing.assert_array_equal(idx, out[(1, 1)][1][0][0])
+                np.testing.assert_array_equal(d, out[(1, 1)][1][0][1])
+        sess.close()
+    after_overflow = 0
+    for prev, cur in zip(counters, counters[1:]):
+        if prev["overflow_waves"] >= max(256, prev["waves"] / 32) and cur["overflow_waves"] > 0:
+            after_overflow += 1
+            assert cur["wide_waves"] > 0, (prev, cur)
+    if which == "scene":  # far from convergence on surface data: the rule is in force
+        assert after_overflow > 0, [(c["waves"], c["overflow_waves"], c["wide_waves"]) for c in counters]
 
 
 def test_scene_vs_reference_fixture(icp, golden_scene, golden_meta):
