@@ -508,6 +508,40 @@ int icp_hip_plane_sums(icp_hip_ctx* ctx, const double origin[3], icp_plane_sums*
  * entry of A is not positive, or a pivot of the scaled matrix is at most 2^-26. */
 void icp_plane_solve(const icp_plane_sums* sums, double T[16], int32_t* ok);
 
+/* --- Voxel-grid down-sampling. Beside everything above: it needs no target and no
+ * source and touches neither.
+ * n points (AoS xyz, fp64), a voxel edge `voxel` and an origin o: the caller's, or with null the
+ * per-axis minimum of the cloud (safe at georeferenced offsets). A point's cell is
+ * c_a = floor((x_a - o_a) / voxel) in fp64 as written, every c_a in [0, 2^21), and its key
+ * cz << 42 | cy << 21 | cx. A voxel is a distinct key; voxels are output in ascending key order and
+ * a voxel's points are taken in ascending original index. Per voxel: count_out, first_out (its
+ * lowest original index) and the point xyz_out: with ICP_VOXEL_FIRST the coordinates of `first`, bit
+ * for bit; with ICP_VOXEL_CENTROID o + s / count, s the sum of d_i = x_i - o over the voxel's points
+ * i = 0..count-1 in a fixed order (64 partials s_l = +0.0 + d_l + d_{l+64} + ..., folded
+ * s_l += s_{l+w}, w = 32, 16, .., 1): a function of the data alone, the same bits from this call,
+ * its _device variant and the host's icp_voxel_downsample (icp_host.h).
+ * The three outputs hold `cap` entries each (3 cap doubles for xyz_out); any may be null, all null
+ * counts only. *m_out is the number of voxels whenever the cells are valid; m > cap with a non-null
+ * output is ICP_HIP_EINVAL with *m_out set and the outputs untouched (cap = n always suffices).
+ * origin_out (may be null) reports the origin in use.
+ * ICP_HIP_EINVAL also for: voxel not finite or <= 0; n < 1 or n > 2^31 - 1; a non-finite coordinate
+ * (the text says how many) or origin; a cell index outside [0, 2^21), i.e. a grid too fine for the
+ * extent or a point below the caller's origin (the text says which); an unknown mode.
+ * The _device variant takes d_xyz and the three outputs in HBM under the contract of the *_device
+ * calls above (origin, m_out and origin_out stay host pointers). A multi-device context runs the
+ * call on its first member. */
+#define ICP_VOXEL_CENTROID 0
+#define ICP_VOXEL_FIRST 1
+int icp_hip_voxel_downsample(icp_hip_ctx* ctx, const double* xyz, int64_t n, double voxel, const double* origin,
+                             int mode, int64_t cap, double* xyz_out, int32_t* first_out, int32_t* count_out,
+                             int64_t* m_out, double origin_out[3]);
+int icp_hip_voxel_downsample_device(icp_hip_ctx* ctx, const double* d_xyz, int64_t n, double voxel,
+                                    const double* origin, int mode, int64_t cap, double* d_xyz_out,
+                                    int32_t* d_first_out, int32_t* d_count_out, int64_t* m_out, double origin_out[3]);
+/* Device milliseconds of the five phases of the context's last successful voxel call (bounds, keys,
+ * sort, runs, reduce; a phase that did not run: 0). ICP_HIP_ENOTREADY before the first one. */
+int icp_hip_voxel_last_timing(icp_hip_ctx* ctx, double ms[5]);
+
 /* Work of the reference DFS for the resident source (node entries and leaf points compared,
  * both as the reference visits them) — the V and P of the roofline byte model. */
 int icp_hip_traversal_counts(icp_hip_ctx* ctx, double* mean_node_entries, double* mean_leaf_points);

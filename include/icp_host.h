@@ -5,6 +5,7 @@
  *   - the rank-merge of per-rank partial statistics (the exchange step of the multi-GPU path)
  *   - a deterministic synthetic cloud-pair generator (the test_icp.cpp:165-229 recipe with a
  *     fixed, counter-based RNG instead of rand()/time())
+ *   - voxel-grid down-sampling, the host statement of icp_hip_voxel_downsample
  */
 #ifndef ICP_HOST_H
 #define ICP_HOST_H
@@ -98,6 +99,15 @@ typedef struct icp_scene_spec {
 void icp_scene_default(icp_scene_spec* s);
 int icp_synth_scene(const icp_scene_spec* s, int64_t n_tgt, int64_t n_src, double* tgt_xyz, double* src_xyz,
                     double T_true[16]);
+
+/* Voxel-grid down-sampling on the host, no GPU: the function of icp_hip_voxel_downsample
+ * (icp_hip.h: cells, keys, order, the centroid's summation order, the rejected inputs), the same
+ * bits. Returns the number of voxels m, or a negative ICP_HIP_E* code with icp_hip_last_error set.
+ * The three outputs hold `cap` entries each; any may be null, all null counts only (the call that
+ * sizes the buffers); m > cap with a non-null output is ICP_HIP_EINVAL. origin null: the cloud's
+ * per-axis minimum; origin_out (may be null) reports the origin in use. */
+int64_t icp_voxel_downsample(const double* xyz, int64_t n, double voxel, const double* origin, int mode, int64_t cap,
+                             double* xyz_out, int32_t* first_out, int32_t* count_out, double origin_out[3]);
 
 #ifdef __cplusplus
 }

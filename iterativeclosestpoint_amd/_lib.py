@@ -29,6 +29,7 @@ COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2  # icp_hip_dev_copy directions
 DBG_SLOTS = 40
 METRIC_POINT, METRIC_PLANE = 0, 1  # icp_engine.h ICP_METRIC_*
 KNN_MAX = 32
+VOXEL_CENTROID, VOXEL_FIRST = 0, 1  # icp_hip.h ICP_VOXEL_*
 # icp_hip.h ICP_DBG_* slot names
 DBG_NAMES = {0: "waves", 1: "overflow_waves", 2: "not_joined", 3: "not_covered", 4: "scanned_points",
              8: "fp64_scan_waves", 9: "staged_points", 10: "scan_pairs", 11: "scan_rounds",
@@ -200,6 +201,11 @@ SIGNATURES = {
     "icp_hip_get_target_normals_device": (C.c_int, [_P, _P]),
     "icp_hip_plane_sums": (C.c_int, [_P, _P, C.POINTER(PlaneSums)]),
     "icp_plane_solve": (None, [C.POINTER(PlaneSums), _P, _I32]),
+    "icp_hip_voxel_downsample": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, C.c_int, C.c_int64, _P, _P, _P,
+                                           C.POINTER(C.c_int64), _P]),
+    "icp_hip_voxel_downsample_device": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, C.c_int, C.c_int64, _P, _P, _P,
+                                                  C.POINTER(C.c_int64), _P]),
+    "icp_hip_voxel_last_timing": (C.c_int, [_P, _P]),
     "icp_hip_traversal_counts": (C.c_int, [_P, _D, _D]),
     "icp_hip_target_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I32, _I32]),
     "icp_hip_last_timing": (C.c_int, [_P, _D, _D]),
@@ -262,6 +268,7 @@ SIGNATURES = {
     "icp_source_shard_order": (C.c_int, [_P, C.c_int64, _P]),
     "icp_scene_default": (None, [C.POINTER(SceneSpec)]),
     "icp_synth_scene": (C.c_int, [C.POINTER(SceneSpec), C.c_int64, C.c_int64, _P, _P, _P]),
+    "icp_voxel_downsample": (C.c_int64, [_P, C.c_int64, C.c_double, _P, C.c_int, C.c_int64, _P, _P, _P, _P]),
     # icp_las.h
     "icp_las_read_header": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(LasHeader)]),
     "icp_las_read": (C.c_int64, [C.c_char_p, C.c_int, C.c_int64, _P, C.POINTER(LasHeader)]),
@@ -538,6 +545,42 @@ class Context:
         _check(lib().icp_hip_plane_sums(self._h, _ptr(o), C.byref(out)))
         return out
 
+    # --- voxel-grid down-sampling (include/icp_hip.h; the host's: voxel_downsample below)
+    def voxel_downsample(self, xyz, voxel, origin=None, mode=VOXEL_CENTROID, cap=None, count_only=False):
+        """The voxels of an (n, 3) cloud: (xyz (m, 3), first (m,), count (m,), origin (3,)), or with
+        count_only (m, origin). cap: the outputs' capacity (default n). An IcpError of a capacity
+        too small carries the number of voxels in its attribute m."""
+        xyz = _aos(xyz)
+        o_in, o_out = _origin3(origin), np.empty(3)
+        m = C.c_int64(0)
+        n = xyz.shape[0]
+        cap = n if cap is None else int(cap)
+        if count_only:
+            _check_voxel(lib().icp_hip_voxel_downsample(self._h, _ptr(xyz), n, voxel, _ptr(o_in), mode, 0, None, None, None,
+                                                        C.byref(m), _ptr(o_out)), m)
+            return m.value, o_out
+        p, f, k = np.empty((max(cap, 1), 3)), np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32)
+        _check_voxel(lib().icp_hip_voxel_downsample(self._h, _ptr(xyz), n, voxel, _ptr(o_in), mode, cap, _ptr(p), _ptr(f),
+                                                    _ptr(k), C.byref(m), _ptr(o_out)), m)
+        return p[: m.value].copy(), f[: m.value].copy(), k[: m.value].copy(), o_out
+
+    def voxel_downsample_device(self, d_xyz, n: int, voxel, origin=None, mode=VOXEL_CENTROID, cap: int = 0,
+                                d_xyz_out=None, d_first_out=None, d_count_out=None):
+        """icp_hip_voxel_downsample_device: the cloud and the outputs (cap entries each; any may be
+        None, all None counts only) in device buffers. Returns (m, origin (3,))."""
+        o_in, o_out = _origin3(origin), np.empty(3)
+        m = C.c_int64(0)
+        _check_voxel(lib().icp_hip_voxel_downsample_device(self._h, _dptr(d_xyz), n, voxel, _ptr(o_in), mode, cap,
+                                                           _dptr(d_xyz_out), _dptr(d_first_out), _dptr(d_count_out),
+                                                           C.byref(m), _ptr(o_out)), m)
+        return m.value, o_out
+
+    def voxel_last_timing(self) -> np.ndarray:
+        """Device ms of the last voxel call's phases: bounds, keys, sort, runs, reduce."""
+        ms = np.zeros(5)
+        _check(lib().icp_hip_voxel_last_timing(self._h, _ptr(ms)))
+        return ms
+
     # --- LAS files to and from device-resident clouds (include/icp_las.h)
     def read_las_device(self, path, rules=1, max_points=0, stride=1):
         """Decode a LAS file into a new DeviceBuffer. Returns (buffer, n points, header)."""
@@ -709,6 +752,36 @@ class Context:
         else:
             rc = lib().icp_engine_run_metric(self._h, C.byref(params), metric, C.byref(res), hist, history_cap, None)
         return rc, res, [hist[k] for k in range(res.n_history)]
+
+
+def _origin3(origin):
+    return None if origin is None else np.ascontiguousarray(origin, np.float64).reshape(3)
+
+
+def _check_voxel(rc: int, m) -> None:
+    """_check, the error carrying the number of voxels the call reported (0: none)."""
+    if rc != 0:
+        e = IcpError(rc, lib().icp_hip_last_error().decode(errors="replace"))
+        e.m = m.value
+        raise e
+
+
+def voxel_downsample(xyz, voxel, origin=None, mode=VOXEL_CENTROID, cap=None, count_only=False):
+    """Voxel-grid down-sampling on the host (icp_voxel_downsample, no GPU): the function of
+    Context.voxel_downsample, the same bits. (xyz (m, 3), first (m,), count (m,), origin (3,)), or
+    with count_only (m, origin)."""
+    xyz = _aos(xyz)
+    o_in, o_out = _origin3(origin), np.empty(3)
+    n = xyz.shape[0]
+    cap = n if cap is None else int(cap)
+    if count_only:
+        m = lib().icp_voxel_downsample(_ptr(xyz), n, voxel, _ptr(o_in), mode, 0, None, None, None, _ptr(o_out))
+        _check(min(m, 0))
+        return m, o_out
+    p, f, k = np.empty((max(cap, 1), 3)), np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32)
+    m = lib().icp_voxel_downsample(_ptr(xyz), n, voxel, _ptr(o_in), mode, cap, _ptr(p), _ptr(f), _ptr(k), _ptr(o_out))
+    _check(min(m, 0))
+    return p[:m].copy(), f[:m].copy(), k[:m].copy(), o_out
 
 
 def _dptr(b):

@@ -1,0 +1,199 @@
+// ctx_voxel.cpp — the context side of voxel-grid down-sampling: the argument
+// checks, the call's scratch, the five phases of voxel_kernels.hip on the context's stream with the
+// two small read-backs between them, and the host and device variants around that core. It reads
+// no target or source of the context and changes none.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "icp_ctx_internal.h"
+#include "voxel_host.h"
+
+using namespace icp;
+
+namespace {
+
+// Start / end events of the five phases (the read-backs between them stay outside the intervals).
+struct PhaseEvents {
+  hipEvent_t ev[10] = {};
+  bool ran[5] = {};
+  PhaseEvents() = default;
+  PhaseEvents(const PhaseEvents&) = delete;
+  PhaseEvents& operator=(const PhaseEvents&) = delete;
+  ~PhaseEvents() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t mark(int k, hipStream_t s) {
+    if (!ev[k]) {
+      const hipError_t e = hipEventCreate(&ev[k]);
+      if (e != hipSuccess) return e;
+    }
+    if (k & 1) ran[k >> 1] = true;
+    return hipEventRecord(ev[k], s);
+  }
+  // after the stream is synchronised
+  hipError_t read(double ms[5]) const {
+    for (int p = 0; p < 5; p++) {
+      float f = 0.0f;
+      if (ran[p]) {
+        const hipError_t e = hipEventElapsedTime(&f, ev[2 * p], ev[2 * p + 1]);
+        if (e != hipSuccess) return e;
+      }
+      ms[p] = f;
+    }
+    return hipSuccess;
+  }
+};
+
+// The call after the pointer checks. d_xyz is device memory. The outputs are the caller's device
+// buffers (to_host false) or host buffers that get the first m entries of scratch ones.
+int voxel_core(icp_hip_ctx* c, const double* d_xyz, int64_t n, double h, const double* origin, int mode, int64_t cap,
+               bool to_host, double* xyz_out, int32_t* first_out, int32_t* count_out, int64_t* m_out,
+               double origin_out[3]) {
+  VoxelHead hd;  // before the scratch: outlives the copies into it
+  std::memset(&hd, 0, sizeof(hd));
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  PhaseEvents ev;
+  DevScratch S;
+  VoxelHead* head = nullptr;
+  double* parts = nullptr;
+  uint64_t *keys = nullptr, *keys_sorted = nullptr;
+  int32_t *idx = nullptr, *idx_sorted = nullptr;
+  uint8_t* tmp = nullptr;
+  size_t tmp_bytes = 0;
+  HIP_TRY(voxel_temp_bytes(n, &tmp_bytes));
+  HIP_TRY(S.alloc(&head, 1));
+  HIP_TRY(S.alloc(&parts, 4 * (size_t)voxel_bounds_parts(n)));
+  HIP_TRY(S.alloc(&keys, (size_t)n));
+  HIP_TRY(S.alloc(&keys_sorted, (size_t)n));
+  HIP_TRY(S.alloc(&idx, (size_t)n + 1));  // later the run starts (n + 1 entries)
+  HIP_TRY(S.alloc(&idx_sorted, (size_t)n));
+  HIP_TRY(S.alloc(&tmp, tmp_bytes));
+
+  HIP_TRY(ev.mark(0, s));
+  HIP_TRY(launch_voxel_bounds(d_xyz, n, origin, parts, head, s));
+  HIP_TRY(ev.mark(1, s));
+  HIP_TRY(ev.mark(2, s));
+  HIP_TRY(launch_voxel_keys(d_xyz, n, h, head, keys, idx, s));
+  HIP_TRY(ev.mark(3, s));
+  HIP_TRY(hipMemcpyAsync(&hd, head, sizeof(hd), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));  // the one read of the flags, before the sort
+  if (hd.n_bad) return fail(ICP_HIP_EINVAL, voxel_nonfinite_text(hd.n_bad));
+  if (hd.flags) return fail(ICP_HIP_EINVAL, voxel_range_text(hd.flags));
+  if (origin_out)
+    for (int a = 0; a < 3; a++) origin_out[a] = hd.origin[a];
+
+  HIP_TRY(ev.mark(4, s));
+  HIP_TRY(launch_voxel_sort(tmp, tmp_bytes, keys, keys_sorted, idx, idx_sorted, n, hd.max_key, s));
+  HIP_TRY(ev.mark(5, s));
+  // the unsorted keys and the identity are spent: their buffers hold the flags, their sum, the starts
+  int32_t* flag = reinterpret_cast<int32_t*>(keys);
+  int32_t* pos = flag + n;
+  int32_t* starts = idx;
+  HIP_TRY(ev.mark(6, s));
+  HIP_TRY(launch_voxel_runs(tmp, tmp_bytes, keys_sorted, n, flag, pos, starts, head, s));
+  HIP_TRY(ev.mark(7, s));
+  HIP_TRY(hipMemcpyAsync(&hd, head, sizeof(hd), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));  // m: the capacity check needs it
+  const int64_t m = hd.m;
+  *m_out = m;
+  const bool any_out = xyz_out || first_out || count_out;
+  if (any_out && m > cap) return fail(ICP_HIP_EINVAL, voxel_cap_text(m, cap));
+
+  if (any_out) {
+    double* dx = xyz_out;
+    int32_t *df = first_out, *dc = count_out;
+    if (to_host) {
+      if (xyz_out) HIP_TRY(S.alloc(&dx, 3 * (size_t)m));
+      if (first_out) HIP_TRY(S.alloc(&df, (size_t)m));
+      if (count_out) HIP_TRY(S.alloc(&dc, (size_t)m));
+    }
+    HIP_TRY(ev.mark(8, s));
+    HIP_TRY(launch_voxel_reduce(d_xyz, idx_sorted, starts, head, m, mode, dx, df, dc, s));
+    HIP_TRY(ev.mark(9, s));
+    if (to_host) {
+      if (xyz_out) HIP_TRY(hipMemcpyAsync(xyz_out, dx, 3 * sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
+      if (first_out) HIP_TRY(hipMemcpyAsync(first_out, df, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
+      if (count_out) HIP_TRY(hipMemcpyAsync(count_out, dc, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  HIP_TRY(ev.read(c->voxel_ms));
+  c->voxel_timed = true;
+  return ICP_HIP_OK;
+}
+
+int voxel_args(icp_hip_ctx* c, const double* xyz, int64_t n, double h, const double* origin, int mode, int64_t* m_out) {
+  if (!c || !m_out) return fail(ICP_HIP_EINVAL, "voxel_downsample: null argument");
+  *m_out = 0;
+  std::string why;
+  if (const int rc = voxel_check_args(n, h, origin, mode, &why)) return fail(rc, why);
+  if (!xyz) return fail(ICP_HIP_EINVAL, "voxel_downsample: null cloud");
+  return ICP_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int icp_hip_voxel_downsample(icp_hip_ctx* c, const double* xyz, int64_t n, double voxel, const double* origin, int mode,
+                             int64_t cap, double* xyz_out, int32_t* first_out, int32_t* count_out, int64_t* m_out,
+                             double origin_out[3]) {
+  if (const int rc = voxel_args(c, xyz, n, voxel, origin, mode, m_out)) return rc;
+  if (c->group)
+    return icp_hip_voxel_downsample(group_member(c, 0), xyz, n, voxel, origin, mode, cap, xyz_out, first_out, count_out,
+                                    m_out, origin_out);
+  HIP_TRY(hipSetDevice(c->device));
+  DevScratch S;
+  double* up = nullptr;
+  HIP_TRY(S.alloc(&up, 3 * (size_t)n));
+  HIP_TRY(hipMemcpyAsync(up, xyz, 3 * sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  return voxel_core(c, up, n, voxel, origin, mode, cap, true, xyz_out, first_out, count_out, m_out, origin_out);
+}
+
+int icp_hip_voxel_downsample_device(icp_hip_ctx* c, const double* d_xyz, int64_t n, double voxel, const double* origin,
+                                    int mode, int64_t cap, double* d_xyz_out, int32_t* d_first_out, int32_t* d_count_out,
+                                    int64_t* m_out, double origin_out[3]) {
+  if (!c || !m_out) return fail(ICP_HIP_EINVAL, "voxel_downsample_device: null argument");
+  *m_out = 0;
+  if (const int rc = check_device_ptr(c, d_xyz, "voxel_downsample_device")) return rc;
+  if (d_xyz_out)
+    if (const int rc = check_device_ptr(c, d_xyz_out, "voxel_downsample_device")) return rc;
+  if (d_first_out)
+    if (const int rc = check_device_ptr(c, d_first_out, "voxel_downsample_device", 4)) return rc;
+  if (d_count_out)
+    if (const int rc = check_device_ptr(c, d_count_out, "voxel_downsample_device", 4)) return rc;
+  if (const int rc = voxel_args(c, d_xyz, n, voxel, origin, mode, m_out)) return rc;
+  if (c->group) {  // the first member, through host memory (the buffers may be another device's)
+    std::vector<double> h;
+    HIP_TRY(stage_down(c, &h, d_xyz, 3 * (size_t)n));
+    int64_t m = 0;
+    int rc = icp_hip_voxel_downsample(group_member(c, 0), h.data(), n, voxel, origin, mode, 0, nullptr, nullptr, nullptr,
+                                      &m, origin_out);
+    *m_out = m;
+    if (rc != ICP_HIP_OK || (!d_xyz_out && !d_first_out && !d_count_out)) return rc;
+    if (m > cap) return fail(ICP_HIP_EINVAL, voxel_cap_text(m, cap));
+    std::vector<double> p(d_xyz_out ? 3 * (size_t)m : 0);
+    std::vector<int32_t> f(d_first_out ? (size_t)m : 0), k(d_count_out ? (size_t)m : 0);
+    rc = icp_hip_voxel_downsample(group_member(c, 0), h.data(), n, voxel, origin, mode, m, d_xyz_out ? p.data() : nullptr,
+                                  d_first_out ? f.data() : nullptr, d_count_out ? k.data() : nullptr, &m, origin_out);
+    if (rc != ICP_HIP_OK) return rc;
+    HIP_TRY(stage_up(c, d_xyz_out, p));
+    HIP_TRY(stage_up(c, d_first_out, f));
+    HIP_TRY(stage_up(c, d_count_out, k));
+    return ICP_HIP_OK;
+  }
+  return voxel_core(c, d_xyz, n, voxel, origin, mode, cap, false, d_xyz_out, d_first_out, d_count_out, m_out, origin_out);
+}
+
+int icp_hip_voxel_last_timing(icp_hip_ctx* c, double ms[5]) {
+  if (!c || !ms) return fail(ICP_HIP_EINVAL, "null argument");
+  if (c->group) return icp_hip_voxel_last_timing(group_member(c, 0), ms);
+  if (!c->voxel_timed) return fail(ICP_HIP_ENOTREADY, "no voxel call has run on this context");
+  std::memcpy(ms, c->voxel_ms, sizeof(c->voxel_ms));
+  return ICP_HIP_OK;
+}
+
+}  // extern "C"

@@ -8,6 +8,7 @@
 #include "icp_ctx_internal.h"
 #include "octree_build.h"
 #include "query_order.h"
+#include "voxel_host.h"
 
 struct icp_octree {
   icp::FlatOctree t;
@@ -270,6 +271,19 @@ int icp_synth_pair(const icp_synth_spec* s, int64_t n_tgt, int64_t n_src, double
     }
   }
   return 0;
+}
+
+int64_t icp_voxel_downsample(const double* xyz, int64_t n, double voxel, const double* origin, int mode, int64_t cap,
+                             double* xyz_out, int32_t* first_out, int32_t* count_out, double origin_out[3]) {
+  int64_t m = 0;
+  std::string why;
+  const int rc = icp::voxel_downsample_host(xyz, n, voxel, origin, mode, cap, xyz_out, first_out, count_out, &m,
+                                            origin_out, &why);
+  if (rc != ICP_HIP_OK) {
+    icp_ctx_set_error(why.c_str());
+    return rc;
+  }
+  return m;
 }
 
 void icp_scene_default(icp_scene_spec* s) {

@@ -167,6 +167,10 @@ struct icp_hip_ctx {
   double* plane_parts = nullptr;  // plane_cap parts + the merged sums (kPlaneSums doubles each)
   int64_t plane_cap = 0;
 
+  // --- voxel-grid down-sampling (ctx_voxel.cpp): the phases' device times of the last call
+  double voxel_ms[5] = {0, 0, 0, 0, 0};
+  bool voxel_timed = false;
+
   // --- multi-device context (icp_hip_create_multi): the member contexts and their driver threads
   // (icp_group.cpp); the single-device fields above are then unused
   struct DeviceGroup* group = nullptr;

@@ -6,7 +6,13 @@
 //   icp_registration [--source Scan_096_origin.las] [--target Scannew_099.las]
 //                    [--sample-rate 50] [--max-iters 20] [--tolerance 1e-2]
 //                    [--outdir .] [--device 0 | --devices 0,1,...] [--device-io] [--pause]
-//                    [--metric point|plane] [--normals-k 16]
+//                    [--metric point|plane] [--normals-k 16] [--voxel X]
+//
+// --voxel X (metres, > 0) reduces each cloud, after the stride sampling, to the centroids of the
+// voxels of edge X of a grid of its own with the origin at the cloud's minimum
+// (icp_voxel_downsample; with --device-io icp_hip_voxel_downsample_device, nothing comes down). The
+// sampled files hold the voxel clouds and the registration runs on the fp64 centroids. Without
+// --sample-rate the stride is then 1. Without the flag every output is unchanged.
 //
 // --metric plane registers with the point-to-plane step (icp_engine_run_metric, ICP_METRIC_PLANE):
 // the target's normals are estimated from --normals-k neighbours once the target is set; the CLI's
@@ -31,6 +37,7 @@
 
 #include "../../include/icp_engine.h"
 #include "../../include/icp_hip.h"
+#include "../../include/icp_host.h"
 #include "../../include/icp_las.h"
 
 namespace {
@@ -47,19 +54,21 @@ struct Args {
   bool pause = false;
   int metric = ICP_METRIC_POINT;
   int normals_k = 16;
+  double voxel = 0.0;  // 0: no voxel grid
 };
 
 [[noreturn]] void usage(const char* prog, int code) {
   std::fprintf(code ? stderr : stdout,
                "usage: %s [--source F] [--target F] [--sample-rate N] [--max-iters N] [--tolerance X]\n"
                "          [--outdir D] [--device N | --devices N,M,...] [--device-io] [--pause]\n"
-               "          [--metric point|plane] [--normals-k N]\n",
+               "          [--metric point|plane] [--normals-k N] [--voxel X]\n",
                prog);
   std::exit(code);
 }
 
 Args parse(int argc, char** argv) {
   Args a;
+  bool rate_given = false;
   for (int i = 1; i < argc; i++) {
     const std::string k = argv[i];
     auto val = [&]() -> const char* {
@@ -68,7 +77,19 @@ Args parse(int argc, char** argv) {
     };
     if (k == "--source") a.source = val();
     else if (k == "--target") a.target = val();
-    else if (k == "--sample-rate") a.sample_rate = std::strtol(val(), nullptr, 10);
+    else if (k == "--sample-rate") {
+      a.sample_rate = std::strtol(val(), nullptr, 10);
+      rate_given = true;
+    }
+    else if (k == "--voxel") {
+      const char* v = val();
+      char* end = nullptr;
+      a.voxel = std::strtod(v, &end);
+      if (end == v || *end != '\0' || !(a.voxel - a.voxel == 0.0) || !(a.voxel > 0.0)) {
+        std::fprintf(stderr, "--voxel must be a finite edge > 0 (metres)\n");
+        usage(argv[0], 2);
+      }
+    }
     else if (k == "--max-iters") a.max_iters = (int)std::strtol(val(), nullptr, 10);
     else if (k == "--tolerance") a.tolerance = std::strtod(val(), nullptr);
     else if (k == "--outdir") a.outdir = val();
@@ -100,6 +121,7 @@ Args parse(int argc, char** argv) {
     else if (k == "-h" || k == "--help") usage(argv[0], 0);
     else usage(argv[0], 2);
   }
+  if (a.voxel > 0.0 && !rate_given) a.sample_rate = 1;
   if (a.sample_rate < 1) {
     std::fprintf(stderr, "--sample-rate must be >= 1\n");
     std::exit(2);
@@ -152,13 +174,50 @@ void print_cloud(int64_t n, const icp_las_header& hdr) {
             << "), offset (" << hdr.offset[0] << ", " << hdr.offset[1] << ", " << hdr.offset[2] << ")" << std::endl;
 }
 
+void print_voxel(const Args& a, int64_t ns0, int64_t ns, int64_t nt0, int64_t nt) {
+  std::cout << "\nvoxel grid (" << a.voxel << " m)..." << std::endl;
+  std::cout << "source: " << ns0 << " -> " << ns << " points\ntarget: " << nt0 << " -> " << nt << " points" << std::endl;
+}
+
+// --voxel, host flow: the cloud replaced by the centroids of its voxels (its own grid, the origin at
+// its minimum).
+bool voxel_reduce(const Args& a, std::vector<double>& xyz) {
+  const int64_t n = (int64_t)xyz.size() / 3;
+  std::vector<double> out(xyz.size());
+  const int64_t m = icp_voxel_downsample(xyz.data(), n, a.voxel, nullptr, ICP_VOXEL_CENTROID, n, out.data(), nullptr,
+                                         nullptr, nullptr);
+  if (m < 0) return false;
+  out.resize((size_t)m * 3);
+  xyz.swap(out);
+  return true;
+}
+
+// --voxel, --device-io flow: *d_xyz (n points, a buffer of icp_hip_dev_alloc) replaced by a buffer of
+// the centroids of its voxels; the old buffer is freed.
+bool voxel_reduce_device(const Args& a, icp_hip_ctx* ctx, void** d_xyz, int64_t* n) {
+  void* d_out = nullptr;
+  int64_t m = 0;
+  if (icp_hip_dev_alloc(ctx, 3 * sizeof(double) * (size_t)*n, &d_out) != ICP_HIP_OK) return false;
+  if (icp_hip_voxel_downsample_device(ctx, static_cast<double*>(*d_xyz), *n, a.voxel, nullptr, ICP_VOXEL_CENTROID, *n,
+                                      static_cast<double*>(d_out), nullptr, nullptr, &m, nullptr) != ICP_HIP_OK) {
+    (void)icp_hip_dev_free(ctx, d_out);
+    return false;
+  }
+  (void)icp_hip_dev_free(ctx, *d_xyz);
+  *d_xyz = d_out;
+  *n = m;
+  return true;
+}
+
 // --device-io: the default flow's steps on clouds that stay in HBM (one context; the same files).
 int run_device_io(const Args& a) {
   icp_hip_ctx* ctx = nullptr;
   void* d_tgt = nullptr;
+  void* d_src = nullptr;  // --voxel only: the decoded source on its way through the voxel grid
   auto bail = [&](const char* msg) {
     std::cerr << msg << ": " << icp_hip_last_error() << std::endl;
     if (ctx) (void)icp_hip_dev_free(ctx, d_tgt);
+    if (ctx) (void)icp_hip_dev_free(ctx, d_src);
     icp_hip_destroy(ctx);
     return fail(a, msg);
   };
@@ -168,7 +227,13 @@ int run_device_io(const Args& a) {
   icp_las_header hs{}, ht{};
   int64_t ns = 0, nt = 0;
   std::cout << "\nsource: " << a.source << std::endl << "  reading " << a.source << std::endl;
-  if (icp_hip_set_source_las(ctx, a.source.c_str(), ICP_LAS_CLI, 0, a.sample_rate, &hs, &ns) != ICP_HIP_OK || ns <= 0)
+  if (a.voxel > 0.0) {  // into a buffer of ours first: the source is set from its voxel cloud below
+    if (icp_hip_read_las_device(ctx, a.source.c_str(), ICP_LAS_CLI, 0, a.sample_rate, nullptr, &hs, &ns) != ICP_HIP_OK ||
+        ns <= 0 || icp_hip_dev_alloc(ctx, 3 * sizeof(double) * (size_t)ns, &d_src) != ICP_HIP_OK ||
+        icp_hip_read_las_device(ctx, a.source.c_str(), ICP_LAS_CLI, 0, a.sample_rate, static_cast<double*>(d_src), &hs,
+                                &ns) != ICP_HIP_OK)
+      return bail("cannot read the source point cloud");
+  } else if (icp_hip_set_source_las(ctx, a.source.c_str(), ICP_LAS_CLI, 0, a.sample_rate, &hs, &ns) != ICP_HIP_OK || ns <= 0)
     return bail("cannot read the source point cloud");
   print_cloud((int64_t)hs.num_points, hs);
   std::cout << "\ntarget: " << a.target << std::endl << "  reading " << a.target << std::endl;
@@ -181,6 +246,15 @@ int run_device_io(const Args& a) {
   print_cloud((int64_t)ht.num_points, ht);
   std::cout << "\ndown-sampling (1/" << a.sample_rate << ")..." << std::endl;
   std::cout << "source: " << ns << " points\ntarget: " << nt << " points" << std::endl;
+  if (a.voxel > 0.0) {
+    const int64_t ns0 = ns, nt0 = nt;
+    if (!voxel_reduce_device(a, ctx, &d_src, &ns) || !voxel_reduce_device(a, ctx, &d_tgt, &nt) ||
+        icp_hip_set_source_device(ctx, static_cast<double*>(d_src), ns) != ICP_HIP_OK)
+      return bail("cannot reduce the clouds to the voxel grid");
+    (void)icp_hip_dev_free(ctx, d_src);
+    d_src = nullptr;
+    print_voxel(a, ns0, ns, nt0, nt);
+  }
 
   // both sampled clouds carry the SOURCE's scale/offset (:862-876)
   if (icp_hip_write_source_las(ctx, out_path(a, "sampled_source.las").c_str(), ICP_LAS_CLI, hs.scale, hs.offset, nullptr) !=
@@ -284,12 +358,21 @@ int main(int argc, char** argv) {
   std::vector<double> ss, ts;
   for (size_t i = 0; i < src.size() / 3; i += (size_t)a.sample_rate) ss.insert(ss.end(), &src[3 * i], &src[3 * i] + 3);
   for (size_t i = 0; i < tgt.size() / 3; i += (size_t)a.sample_rate) ts.insert(ts.end(), &tgt[3 * i], &tgt[3 * i] + 3);
-  const int64_t ns = (int64_t)ss.size() / 3, nt = (int64_t)ts.size() / 3;
+  int64_t ns = (int64_t)ss.size() / 3, nt = (int64_t)ts.size() / 3;
   std::cout << "source: " << ns << " points\ntarget: " << nt << " points" << std::endl;
   src.clear();
   src.shrink_to_fit();
   tgt.clear();
   tgt.shrink_to_fit();
+  if (a.voxel > 0.0) {
+    const int64_t ns0 = ns, nt0 = nt;
+    if (!voxel_reduce(a, ss) || !voxel_reduce(a, ts)) {
+      std::cerr << "voxel grid: " << icp_hip_last_error() << std::endl;
+      return fail(a, "cannot reduce the clouds to the voxel grid");
+    }
+    ns = (int64_t)ss.size() / 3, nt = (int64_t)ts.size() / 3;
+    print_voxel(a, ns0, ns, nt0, nt);
+  }
 
   if (icp_las_write_cli(out_path(a, "sampled_source.las").c_str(), ss.data(), ns, hs.scale, hs.offset) != 0 ||
       icp_las_write_cli(out_path(a, "sampled_target.las").c_str(), ts.data(), nt, hs.scale, hs.offset) != 0)

@@ -253,6 +253,38 @@ struct PlaneLaunch {
 int64_t plane_num_parts(int64_t n);
 hipError_t launch_plane_sums(const PlaneLaunch& a, hipStream_t s);
 
+// --- voxel_kernels.hip: voxel-grid down-sampling (the definition: voxel_host.h).
+struct VoxelOrigin {
+  double o[3];
+};
+// The call's device-resident record: what the host reads back (once after the keys, once after the runs).
+struct VoxelHead {
+  double origin[3];            // the origin in use (phase 1)
+  unsigned long long n_bad;    // non-finite coordinates (phase 1)
+  unsigned long long max_key;  // the largest key (phase 2): the sort's end bit
+  unsigned flags;              // kVoxelBelow | kVoxelBeyond: a cell index outside [0, 2^21) (phase 2)
+  int32_t m;                   // runs = voxels (phase 4)
+};
+int voxel_bounds_parts(int64_t n);                      // parts of phase 1 (4 doubles each)
+hipError_t voxel_temp_bytes(int64_t n, size_t* bytes);  // hipCUB's scratch for the sort and the scan
+// Phase 1: head->origin = origin, or (null) the cloud's per-axis minimum; head->n_bad; the rest cleared.
+hipError_t launch_voxel_bounds(const double* xyz, int64_t n, const double* origin, double* parts, VoxelHead* head,
+                               hipStream_t s);
+// Phase 2: keys[i] and idx[i] = i of every point; head->max_key, head->flags.
+hipError_t launch_voxel_keys(const double* xyz, int64_t n, double h, VoxelHead* head, uint64_t* keys, int32_t* idx,
+                             hipStream_t s);
+// Phase 3: the stable radix sort of (key, index) over the bits of max_key.
+hipError_t launch_voxel_sort(void* tmp, size_t tmp_bytes, const uint64_t* keys, uint64_t* keys_out, const int32_t* idx,
+                             int32_t* idx_out, int64_t n, uint64_t max_key, hipStream_t s);
+// Phase 4: flag / pos (n ints each, scratch), starts (n + 1 ints: run r begins at slot starts[r],
+// starts[m] = n) and head->m.
+hipError_t launch_voxel_runs(void* tmp, size_t tmp_bytes, const uint64_t* sorted_keys, int64_t n, int32_t* flag,
+                             int32_t* pos, int32_t* starts, VoxelHead* head, hipStream_t s);
+// Phase 5: per run its first index, count and point (any output may be null).
+hipError_t launch_voxel_reduce(const double* xyz, const int32_t* idx, const int32_t* starts, const VoxelHead* head,
+                               int64_t m, int mode, double* xyz_out, int32_t* first_out, int32_t* count_out,
+                               hipStream_t s);
+
 hipError_t launch_apply(const double T[12], double* x, double* y, double* z, int64_t n, hipStream_t s);
 hipError_t launch_scatter_aos(const int32_t* perm, const double* x, const double* y, const double* z,
                               double* aos, int64_t n, hipStream_t s);
