@@ -596,6 +596,49 @@ int icp_hip_debug_inject_failure(icp_hip_ctx* ctx, int member, int where);
 
 const char* icp_hip_last_error(void);
 
+/* --- Outlier removal. Beside everything above: it needs no target and no source
+ * and touches neither. n points (AoS xyz, fp64), fl(d2_ij) = dx*dx + dy*dy + dz*dz left to right in
+ * fp64 without FMA, and a mode:
+ * ICP_OUTLIER_STATISTICAL (k, param = std_ratio). The neighbours of point i are the k points j != i
+ * smallest under (fl(d2_ij), j), ascending: the k-NN's tie rule with the point itself excluded by
+ * index (copies of i are neighbours at distance 0). score_i = (sqrt(d2_0) + ... + sqrt(d2_{k-1})) / k,
+ * added in neighbour order, each root correctly rounded. mean = sum score_i / n,
+ * std = sqrt(sum (score_i - mean)^2 / n) (the population form, as the loop's cull; PCL's
+ * StatisticalOutlierRemoval divides by n - 1), threshold = mean + std_ratio * std. Point i is kept iff
+ * score_i <= threshold. mean and std come from a fixed reduction over the scores in original index
+ * order: the same bits from every call, whatever the context's configuration.
+ * k in [1, min(ICP_HIP_KNN_MAX, n - 1)]; std_ratio finite.
+ * ICP_OUTLIER_RADIUS (k = minimum neighbours, param = radius). r2 = fl(radius * radius),
+ * score_i = min(k, #{j != i : fl(d2_ij) <= r2}); point i is kept iff score_i == k. k in [1, n - 1];
+ * radius finite and > 0. stats: mean and std of the saturated counts, threshold = k.
+ * Outputs: the kept points in ascending original index, index_out (cap entries) and xyz_out (3 cap
+ * doubles, the coordinates bit for bit); score_out (n doubles, the caller's order, kept and dropped
+ * alike); *m_out the number kept; *stats. Any output but m_out may be null. m > cap with a non-null
+ * xyz_out or index_out is ICP_HIP_EINVAL with *m_out set and nothing written (cap = n always
+ * suffices). ICP_HIP_EINVAL, before any output, also for: n < 2 or n > 2^31 - 1; k out of range; a
+ * non-finite std_ratio; a radius not finite or <= 0; a non-finite coordinate; an unknown mode.
+ * The _device variant takes d_xyz and the three array outputs in HBM under the contract of the
+ * *_device calls above (m_out and stats stay host pointers). A multi-device context runs the call on
+ * its first member. */
+#define ICP_OUTLIER_STATISTICAL 0
+#define ICP_OUTLIER_RADIUS 1
+typedef struct icp_outlier_stats {
+  int64_t n;        /* points in */
+  int64_t kept;     /* points kept (= *m_out) */
+  double mean;      /* of the scores */
+  double std;       /* population standard deviation of the scores */
+  double threshold; /* statistical: mean + std_ratio * std; radius: k */
+} icp_outlier_stats;
+int icp_hip_outlier_filter(icp_hip_ctx* ctx, const double* xyz, int64_t n, int mode, int k, double param, int64_t cap,
+                           double* xyz_out, int32_t* index_out, double* score_out, int64_t* m_out,
+                           icp_outlier_stats* stats);
+int icp_hip_outlier_filter_device(icp_hip_ctx* ctx, const double* d_xyz, int64_t n, int mode, int k, double param,
+                                  int64_t cap, double* d_xyz_out, int32_t* d_index_out, double* d_score_out,
+                                  int64_t* m_out, icp_outlier_stats* stats);
+/* Device milliseconds of the four phases of the context's last successful outlier call (octree build,
+ * scores, statistics, compaction). ICP_HIP_ENOTREADY before the first one. */
+int icp_hip_outlier_last_timing(icp_hip_ctx* ctx, double ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

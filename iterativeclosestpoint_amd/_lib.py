@@ -30,6 +30,7 @@ DBG_SLOTS = 40
 METRIC_POINT, METRIC_PLANE = 0, 1  # icp_engine.h ICP_METRIC_*
 KNN_MAX = 32
 VOXEL_CENTROID, VOXEL_FIRST = 0, 1  # icp_hip.h ICP_VOXEL_*
+OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1  # icp_hip.h ICP_OUTLIER_*
 # icp_hip.h ICP_DBG_* slot names
 DBG_NAMES = {0: "waves", 1: "overflow_waves", 2: "not_joined", 3: "not_covered", 4: "scanned_points",
              8: "fp64_scan_waves", 9: "staged_points", 10: "scan_pairs", 11: "scan_rounds",
@@ -161,6 +162,12 @@ class PlaneSums(C.Structure):
     ]
 
 
+class OutlierStats(C.Structure):
+    """icp_outlier_stats (include/icp_hip.h): what an outlier call reports beside its arrays."""
+    _fields_ = [("n", C.c_int64), ("kept", C.c_int64), ("mean", C.c_double), ("std", C.c_double),
+                ("threshold", C.c_double)]
+
+
 _EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double))
 
 # (name, restype, argtypes) for every exported symbol; also the list the ABI test checks
@@ -206,6 +213,11 @@ SIGNATURES = {
     "icp_hip_voxel_downsample_device": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, C.c_int, C.c_int64, _P, _P, _P,
                                                   C.POINTER(C.c_int64), _P]),
     "icp_hip_voxel_last_timing": (C.c_int, [_P, _P]),
+    "icp_hip_outlier_filter": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int64, _P, _P, _P, _P,
+                                         _P]),
+    "icp_hip_outlier_filter_device": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int64, _P, _P, _P,
+                                                _P, _P]),
+    "icp_hip_outlier_last_timing": (C.c_int, [_P, _P]),
     "icp_hip_traversal_counts": (C.c_int, [_P, _D, _D]),
     "icp_hip_target_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I32, _I32]),
     "icp_hip_last_timing": (C.c_int, [_P, _D, _D]),
@@ -581,6 +593,37 @@ class Context:
         _check(lib().icp_hip_voxel_last_timing(self._h, _ptr(ms)))
         return ms
 
+    # --- outlier removal (include/icp_hip.h)
+    def outlier_filter(self, xyz, mode, k, param, cap=None):
+        """The points of an (n, 3) cloud that the statistical (k, std_ratio) or the radius (minimum
+        neighbours, radius) filter keeps: (xyz (m, 3), index (m,), score (n,), stats). cap: the
+        kept outputs' capacity (default n). An IcpError of a capacity too small carries the number
+        kept in its attribute m."""
+        xyz = _aos(xyz)
+        n = xyz.shape[0]
+        cap = n if cap is None else int(cap)
+        m, st = C.c_int64(0), OutlierStats()
+        p, ix, sc = np.empty((max(cap, 1), 3)), np.empty(max(cap, 1), np.int32), np.empty(max(n, 1))
+        _check_voxel(lib().icp_hip_outlier_filter(self._h, _ptr(xyz), n, mode, k, param, cap, _ptr(p), _ptr(ix), _ptr(sc),
+                                                  C.byref(m), C.byref(st)), m)
+        return p[: m.value].copy(), ix[: m.value].copy(), sc[:n], st
+
+    def outlier_filter_device(self, d_xyz, n: int, mode, k, param, cap: int = 0, d_xyz_out=None, d_index_out=None,
+                              d_score_out=None):
+        """icp_hip_outlier_filter_device: the cloud and the outputs (cap kept entries, n scores; any
+        may be None, all None counts only) in device buffers. Returns (m, stats)."""
+        m, st = C.c_int64(0), OutlierStats()
+        _check_voxel(lib().icp_hip_outlier_filter_device(self._h, _dptr(d_xyz), n, mode, k, param, cap, _dptr(d_xyz_out),
+                                                         _dptr(d_index_out), _dptr(d_score_out), C.byref(m),
+                                                         C.byref(st)), m)
+        return m.value, st
+
+    def outlier_last_timing(self) -> np.ndarray:
+        """Device ms of the last outlier call's phases: octree build, scores, statistics, compaction."""
+        ms = np.zeros(4)
+        _check(lib().icp_hip_outlier_last_timing(self._h, _ptr(ms)))
+        return ms
+
     # --- LAS files to and from device-resident clouds (include/icp_las.h)
     def read_las_device(self, path, rules=1, max_points=0, stride=1):
         """Decode a LAS file into a new DeviceBuffer. Returns (buffer, n points, header)."""
@@ -782,6 +825,13 @@ def voxel_downsample(xyz, voxel, origin=None, mode=VOXEL_CENTROID, cap=None, cou
     m = lib().icp_voxel_downsample(_ptr(xyz), n, voxel, _ptr(o_in), mode, cap, _ptr(p), _ptr(f), _ptr(k), _ptr(o_out))
     _check(min(m, 0))
     return p[:m].copy(), f[:m].copy(), k[:m].copy(), o_out
+
+
+def outlier_filter(xyz, mode, k, param, cap=None, device: int = 0):
+    """Context.outlier_filter on a context of its own on `device` (the filters run on the GPU only):
+    (xyz (m, 3), index (m,), score (n,), stats)."""
+    with Context(device) as ctx:
+        return ctx.outlier_filter(xyz, mode, k, param, cap)
 
 
 def _dptr(b):

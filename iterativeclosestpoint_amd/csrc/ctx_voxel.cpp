@@ -7,44 +7,12 @@
 #include <vector>
 
 #include "icp_ctx_internal.h"
+#include "phase_events.h"
 #include "voxel_host.h"
 
 using namespace icp;
 
 namespace {
-
-// Start / end events of the five phases (the read-backs between them stay outside the intervals).
-struct PhaseEvents {
-  hipEvent_t ev[10] = {};
-  bool ran[5] = {};
-  PhaseEvents() = default;
-  PhaseEvents(const PhaseEvents&) = delete;
-  PhaseEvents& operator=(const PhaseEvents&) = delete;
-  ~PhaseEvents() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  hipError_t mark(int k, hipStream_t s) {
-    if (!ev[k]) {
-      const hipError_t e = hipEventCreate(&ev[k]);
-      if (e != hipSuccess) return e;
-    }
-    if (k & 1) ran[k >> 1] = true;
-    return hipEventRecord(ev[k], s);
-  }
-  // after the stream is synchronised
-  hipError_t read(double ms[5]) const {
-    for (int p = 0; p < 5; p++) {
-      float f = 0.0f;
-      if (ran[p]) {
-        const hipError_t e = hipEventElapsedTime(&f, ev[2 * p], ev[2 * p + 1]);
-        if (e != hipSuccess) return e;
-      }
-      ms[p] = f;
-    }
-    return hipSuccess;
-  }
-};
 
 // The call after the pointer checks. d_xyz is device memory. The outputs are the caller's device
 // buffers (to_host false) or host buffers that get the first m entries of scratch ones.
@@ -55,7 +23,7 @@ int voxel_core(icp_hip_ctx* c, const double* d_xyz, int64_t n, double h, const d
   std::memset(&hd, 0, sizeof(hd));
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  PhaseEvents ev;
+  PhaseEvents<5> ev;  // bounds, keys, sort, runs, reduce
   DevScratch S;
   VoxelHead* head = nullptr;
   double* parts = nullptr;

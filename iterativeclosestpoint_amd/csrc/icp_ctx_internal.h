@@ -171,6 +171,10 @@ struct icp_hip_ctx {
   double voxel_ms[5] = {0, 0, 0, 0, 0};
   bool voxel_timed = false;
 
+  // --- outlier removal (ctx_outlier.cpp): the phases' device times of the last call
+  double outlier_ms[4] = {0, 0, 0, 0};
+  bool outlier_timed = false;
+
   // --- multi-device context (icp_hip_create_multi): the member contexts and their driver threads
   // (icp_group.cpp); the single-device fields above are then unused
   struct DeviceGroup* group = nullptr;

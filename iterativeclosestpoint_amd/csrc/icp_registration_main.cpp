@@ -7,12 +7,20 @@
 //                    [--sample-rate 50] [--max-iters 20] [--tolerance 1e-2]
 //                    [--outdir .] [--device 0 | --devices 0,1,...] [--device-io] [--pause]
 //                    [--metric point|plane] [--normals-k 16] [--voxel X]
+//                    [--sor K,RATIO] [--radius-filter R,MIN]
 //
 // --voxel X (metres, > 0) reduces each cloud, after the stride sampling, to the centroids of the
 // voxels of edge X of a grid of its own with the origin at the cloud's minimum
 // (icp_voxel_downsample; with --device-io icp_hip_voxel_downsample_device, nothing comes down). The
 // sampled files hold the voxel clouds and the registration runs on the fp64 centroids. Without
 // --sample-rate the stride is then 1. Without the flag every output is unchanged.
+//
+// --sor K,RATIO drops from each cloud the points whose mean distance to their K nearest other points
+// exceeds mean + RATIO * std of those scores; --radius-filter R,MIN those with fewer than MIN other
+// points within R metres (icp_hip_outlier_filter; with --device-io its _device variant, nothing
+// comes down). Each runs on each cloud after the stride and after --voxel, before the normals and
+// the loop; with both flags the radius filter runs first. The sampled files hold the filtered
+// clouds. Without the flags every output is unchanged.
 //
 // --metric plane registers with the point-to-plane step (icp_engine_run_metric, ICP_METRIC_PLANE):
 // the target's normals are estimated from --normals-k neighbours once the target is set; the CLI's
@@ -55,13 +63,19 @@ struct Args {
   int metric = ICP_METRIC_POINT;
   int normals_k = 16;
   double voxel = 0.0;  // 0: no voxel grid
+  int sor_k = 0;       // 0: no statistical filter
+  double sor_ratio = 0.0;
+  double radius = 0.0;  // 0: no radius filter
+  int radius_min = 0;
+  bool filtered() const { return sor_k > 0 || radius > 0.0; }
 };
 
 [[noreturn]] void usage(const char* prog, int code) {
   std::fprintf(code ? stderr : stdout,
                "usage: %s [--source F] [--target F] [--sample-rate N] [--max-iters N] [--tolerance X]\n"
                "          [--outdir D] [--device N | --devices N,M,...] [--device-io] [--pause]\n"
-               "          [--metric point|plane] [--normals-k N] [--voxel X]\n",
+               "          [--metric point|plane] [--normals-k N] [--voxel X]\n"
+               "          [--sor K,RATIO] [--radius-filter R,MIN]\n",
                prog);
   std::exit(code);
 }
@@ -89,6 +103,31 @@ Args parse(int argc, char** argv) {
         std::fprintf(stderr, "--voxel must be a finite edge > 0 (metres)\n");
         usage(argv[0], 2);
       }
+    }
+    else if (k == "--sor") {
+      const char* v = val();
+      char *e1 = nullptr, *e2 = nullptr;
+      const long kk = std::strtol(v, &e1, 10);
+      if (e1 != v && *e1 == ',') a.sor_ratio = std::strtod(e1 + 1, &e2);
+      if (e1 == v || *e1 != ',' || e2 == e1 + 1 || *e2 != '\0' || !(a.sor_ratio - a.sor_ratio == 0.0) || kk < 1 ||
+          kk > ICP_HIP_KNN_MAX) {
+        std::fprintf(stderr, "--sor must be K,RATIO with K in [1, %d] and a finite RATIO\n", ICP_HIP_KNN_MAX);
+        usage(argv[0], 2);
+      }
+      a.sor_k = (int)kk;
+    }
+    else if (k == "--radius-filter") {
+      const char* v = val();
+      char *e1 = nullptr, *e2 = nullptr;
+      long mm = 0;
+      a.radius = std::strtod(v, &e1);
+      if (e1 != v && *e1 == ',') mm = std::strtol(e1 + 1, &e2, 10);
+      if (e1 == v || *e1 != ',' || e2 == e1 + 1 || *e2 != '\0' || !(a.radius - a.radius == 0.0) || !(a.radius > 0.0) ||
+          mm < 1 || mm > 0x7fffffffL) {
+        std::fprintf(stderr, "--radius-filter must be R,MIN with a finite R > 0 (metres) and MIN >= 1\n");
+        usage(argv[0], 2);
+      }
+      a.radius_min = (int)mm;
     }
     else if (k == "--max-iters") a.max_iters = (int)std::strtol(val(), nullptr, 10);
     else if (k == "--tolerance") a.tolerance = std::strtod(val(), nullptr);
@@ -209,11 +248,76 @@ bool voxel_reduce_device(const Args& a, icp_hip_ctx* ctx, void** d_xyz, int64_t*
   return true;
 }
 
+// One outlier filter's line: the points before, the points kept and the threshold.
+void print_outlier(const char* cloud, const char* what, const icp_outlier_stats& st) {
+  std::cout << "  " << cloud << " (" << what << "): " << st.n << " -> " << st.kept << " points, threshold " << st.threshold
+            << std::endl;
+}
+
+void print_outlier_head(const Args& a) {
+  std::cout << "\noutlier removal (";
+  if (a.radius > 0.0) std::cout << "radius " << a.radius << " m, at least " << a.radius_min << (a.sor_k > 0 ? "; " : "");
+  if (a.sor_k > 0) std::cout << "statistical, k=" << a.sor_k << ", ratio " << a.sor_ratio;
+  std::cout << ")..." << std::endl;
+}
+
+// The filters of the flags in their order (radius, then statistical) as (mode, k, param, name).
+struct OutlierPass {
+  int mode, k;
+  double param;
+  const char* what;
+};
+std::vector<OutlierPass> outlier_passes(const Args& a) {
+  std::vector<OutlierPass> v;
+  if (a.radius > 0.0) v.push_back({ICP_OUTLIER_RADIUS, a.radius_min, a.radius, "radius"});
+  if (a.sor_k > 0) v.push_back({ICP_OUTLIER_STATISTICAL, a.sor_k, a.sor_ratio, "statistical"});
+  return v;
+}
+
+// --sor / --radius-filter, host flow: the cloud replaced by its kept points, through the device call.
+bool outlier_reduce(const Args& a, icp_hip_ctx* ctx, const char* cloud, std::vector<double>& xyz) {
+  for (const OutlierPass& f : outlier_passes(a)) {
+    const int64_t n = (int64_t)xyz.size() / 3;
+    std::vector<double> out(xyz.size());
+    int64_t m = 0;
+    icp_outlier_stats st{};
+    if (icp_hip_outlier_filter(ctx, xyz.data(), n, f.mode, f.k, f.param, n, out.data(), nullptr, nullptr, &m, &st) !=
+        ICP_HIP_OK)
+      return false;
+    out.resize((size_t)m * 3);
+    xyz.swap(out);
+    print_outlier(cloud, f.what, st);
+  }
+  return true;
+}
+
+// --sor / --radius-filter, --device-io flow: *d_xyz (n points, a buffer of icp_hip_dev_alloc) replaced
+// by a buffer of its kept points; the old buffer is freed.
+bool outlier_reduce_device(const Args& a, icp_hip_ctx* ctx, const char* cloud, void** d_xyz, int64_t* n) {
+  for (const OutlierPass& f : outlier_passes(a)) {
+    void* d_out = nullptr;
+    int64_t m = 0;
+    icp_outlier_stats st{};
+    if (icp_hip_dev_alloc(ctx, 3 * sizeof(double) * (size_t)*n, &d_out) != ICP_HIP_OK) return false;
+    if (icp_hip_outlier_filter_device(ctx, static_cast<double*>(*d_xyz), *n, f.mode, f.k, f.param, *n,
+                                      static_cast<double*>(d_out), nullptr, nullptr, &m, &st) != ICP_HIP_OK) {
+      (void)icp_hip_dev_free(ctx, d_out);
+      return false;
+    }
+    (void)icp_hip_dev_free(ctx, *d_xyz);
+    *d_xyz = d_out;
+    *n = m;
+    print_outlier(cloud, f.what, st);
+  }
+  return true;
+}
+
 // --device-io: the default flow's steps on clouds that stay in HBM (one context; the same files).
 int run_device_io(const Args& a) {
   icp_hip_ctx* ctx = nullptr;
   void* d_tgt = nullptr;
-  void* d_src = nullptr;  // --voxel only: the decoded source on its way through the voxel grid
+  void* d_src = nullptr;  // --voxel and the outlier filters: the decoded source on its way through them
+  const bool staged = a.voxel > 0.0 || a.filtered();
   auto bail = [&](const char* msg) {
     std::cerr << msg << ": " << icp_hip_last_error() << std::endl;
     if (ctx) (void)icp_hip_dev_free(ctx, d_tgt);
@@ -227,7 +331,7 @@ int run_device_io(const Args& a) {
   icp_las_header hs{}, ht{};
   int64_t ns = 0, nt = 0;
   std::cout << "\nsource: " << a.source << std::endl << "  reading " << a.source << std::endl;
-  if (a.voxel > 0.0) {  // into a buffer of ours first: the source is set from its voxel cloud below
+  if (staged) {  // into a buffer of ours first: the source is set from its reduced cloud below
     if (icp_hip_read_las_device(ctx, a.source.c_str(), ICP_LAS_CLI, 0, a.sample_rate, nullptr, &hs, &ns) != ICP_HIP_OK ||
         ns <= 0 || icp_hip_dev_alloc(ctx, 3 * sizeof(double) * (size_t)ns, &d_src) != ICP_HIP_OK ||
         icp_hip_read_las_device(ctx, a.source.c_str(), ICP_LAS_CLI, 0, a.sample_rate, static_cast<double*>(d_src), &hs,
@@ -248,12 +352,20 @@ int run_device_io(const Args& a) {
   std::cout << "source: " << ns << " points\ntarget: " << nt << " points" << std::endl;
   if (a.voxel > 0.0) {
     const int64_t ns0 = ns, nt0 = nt;
-    if (!voxel_reduce_device(a, ctx, &d_src, &ns) || !voxel_reduce_device(a, ctx, &d_tgt, &nt) ||
-        icp_hip_set_source_device(ctx, static_cast<double*>(d_src), ns) != ICP_HIP_OK)
+    if (!voxel_reduce_device(a, ctx, &d_src, &ns) || !voxel_reduce_device(a, ctx, &d_tgt, &nt))
       return bail("cannot reduce the clouds to the voxel grid");
+    print_voxel(a, ns0, ns, nt0, nt);
+  }
+  if (a.filtered()) {
+    print_outlier_head(a);
+    if (!outlier_reduce_device(a, ctx, "source", &d_src, &ns) || !outlier_reduce_device(a, ctx, "target", &d_tgt, &nt))
+      return bail("cannot filter the clouds");
+  }
+  if (staged) {
+    if (icp_hip_set_source_device(ctx, static_cast<double*>(d_src), ns) != ICP_HIP_OK)
+      return bail(a.voxel > 0.0 ? "cannot reduce the clouds to the voxel grid" : "cannot filter the clouds");
     (void)icp_hip_dev_free(ctx, d_src);
     d_src = nullptr;
-    print_voxel(a, ns0, ns, nt0, nt);
   }
 
   // both sampled clouds carry the SOURCE's scale/offset (:862-876)
@@ -372,6 +484,18 @@ int main(int argc, char** argv) {
     }
     ns = (int64_t)ss.size() / 3, nt = (int64_t)ts.size() / 3;
     print_voxel(a, ns0, ns, nt0, nt);
+  }
+  if (a.filtered()) {
+    print_outlier_head(a);
+    icp_hip_ctx* fctx = nullptr;
+    const bool ok = icp_hip_create(&fctx, a.devices[0]) == ICP_HIP_OK && outlier_reduce(a, fctx, "source", ss) &&
+                    outlier_reduce(a, fctx, "target", ts);
+    icp_hip_destroy(fctx);
+    if (!ok) {
+      std::cerr << "outlier removal: " << icp_hip_last_error() << std::endl;
+      return fail(a, "cannot filter the clouds");
+    }
+    ns = (int64_t)ss.size() / 3, nt = (int64_t)ts.size() / 3;
   }
 
   if (icp_las_write_cli(out_path(a, "sampled_source.las").c_str(), ss.data(), ns, hs.scale, hs.offset) != 0 ||

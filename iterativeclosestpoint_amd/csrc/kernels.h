@@ -285,6 +285,32 @@ hipError_t launch_voxel_reduce(const double* xyz, const int32_t* idx, const int3
                                int64_t m, int mode, double* xyz_out, int32_t* first_out, int32_t* count_out,
                                hipStream_t s);
 
+// --- outlier_kernels.hip: statistical and radius outlier removal (the definition:
+// icp_hip.h) over a private octree of the cloud (nodes, pts: gpu_build_octree's arrays).
+// The call's device-resident record: what the host reads back (once after the statistics, once
+// after the flags' sum).
+struct OutlierHead {
+  double mean, sd, threshold;  // of the scores (statistics)
+  int32_t m;                   // kept points (compaction)
+  int32_t pad;
+};
+int outlier_num_parts(int64_t n);                         // parts of the statistics (2 doubles each)
+hipError_t outlier_temp_bytes(int64_t n, size_t* bytes);  // hipCUB's scratch for the scan
+// score[original index] of every point: the mean distance to its k nearest other points
+// (ICP_OUTLIER_STATISTICAL; param unused), or the number of other points within the radius param,
+// saturated at k (ICP_OUTLIER_RADIUS). knn_block_threads sizes the blocks (the radius mode: no list).
+hipError_t launch_outlier_scores(const NodeRec* nodes, const TgtPt* pts, int levels, int64_t n, int mode, int k,
+                                 double param, double* score, hipStream_t s);
+// head->mean, sd, threshold from the scores in index order (parts: scratch); head->m cleared.
+hipError_t launch_outlier_stats(const double* score, int64_t n, int mode, int k, double param, double* parts,
+                                OutlierHead* head, hipStream_t s);
+// flag / pos (n ints each): the kept points' flags from head->threshold and their exclusive sum; head->m.
+hipError_t launch_outlier_flags(void* tmp, size_t tmp_bytes, const double* score, int64_t n, int mode, int32_t* flag,
+                                int32_t* pos, OutlierHead* head, hipStream_t s);
+// The kept points' coordinates and original indices at their ranks (either output may be null).
+hipError_t launch_outlier_gather(const double* xyz, int64_t n, const int32_t* flag, const int32_t* pos, double* xyz_out,
+                                 int32_t* index_out, hipStream_t s);
+
 hipError_t launch_apply(const double T[12], double* x, double* y, double* z, int64_t n, hipStream_t s);
 hipError_t launch_scatter_aos(const int32_t* perm, const double* x, const double* y, const double* z,
                               double* aos, int64_t n, hipStream_t s);
