@@ -568,13 +568,13 @@ class Context:
         n = xyz.shape[0]
         cap = n if cap is None else int(cap)
         if count_only:
-            _check_voxel(lib().icp_hip_voxel_downsample(self._h, _ptr(xyz), n, voxel, _ptr(o_in), mode, 0, None, None, None,
-                                                        C.byref(m), _ptr(o_out)), m)
+            _check_m(lib().icp_hip_voxel_downsample(self._h, _ptr(xyz), n, voxel, _ptr(o_in), mode, 0, None, None, None,
+                                                    C.byref(m), _ptr(o_out)), m)
             return m.value, o_out
-        p, f, k = np.empty((max(cap, 1), 3)), np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32)
-        _check_voxel(lib().icp_hip_voxel_downsample(self._h, _ptr(xyz), n, voxel, _ptr(o_in), mode, cap, _ptr(p), _ptr(f),
-                                                    _ptr(k), C.byref(m), _ptr(o_out)), m)
-        return p[: m.value].copy(), f[: m.value].copy(), k[: m.value].copy(), o_out
+        p, f, k = _kept(cap, np.int32, np.int32)
+        _check_m(lib().icp_hip_voxel_downsample(self._h, _ptr(xyz), n, voxel, _ptr(o_in), mode, cap, _ptr(p), _ptr(f),
+                                                _ptr(k), C.byref(m), _ptr(o_out)), m)
+        return *(a[: m.value].copy() for a in (p, f, k)), o_out
 
     def voxel_downsample_device(self, d_xyz, n: int, voxel, origin=None, mode=VOXEL_CENTROID, cap: int = 0,
                                 d_xyz_out=None, d_first_out=None, d_count_out=None):
@@ -582,9 +582,9 @@ class Context:
         None, all None counts only) in device buffers. Returns (m, origin (3,))."""
         o_in, o_out = _origin3(origin), np.empty(3)
         m = C.c_int64(0)
-        _check_voxel(lib().icp_hip_voxel_downsample_device(self._h, _dptr(d_xyz), n, voxel, _ptr(o_in), mode, cap,
-                                                           _dptr(d_xyz_out), _dptr(d_first_out), _dptr(d_count_out),
-                                                           C.byref(m), _ptr(o_out)), m)
+        _check_m(lib().icp_hip_voxel_downsample_device(self._h, _dptr(d_xyz), n, voxel, _ptr(o_in), mode, cap,
+                                                       _dptr(d_xyz_out), _dptr(d_first_out), _dptr(d_count_out),
+                                                       C.byref(m), _ptr(o_out)), m)
         return m.value, o_out
 
     def voxel_last_timing(self) -> np.ndarray:
@@ -603,9 +603,9 @@ class Context:
         n = xyz.shape[0]
         cap = n if cap is None else int(cap)
         m, st = C.c_int64(0), OutlierStats()
-        p, ix, sc = np.empty((max(cap, 1), 3)), np.empty(max(cap, 1), np.int32), np.empty(max(n, 1))
-        _check_voxel(lib().icp_hip_outlier_filter(self._h, _ptr(xyz), n, mode, k, param, cap, _ptr(p), _ptr(ix), _ptr(sc),
-                                                  C.byref(m), C.byref(st)), m)
+        (p, ix), sc = _kept(cap, np.int32), np.empty(max(n, 1))
+        _check_m(lib().icp_hip_outlier_filter(self._h, _ptr(xyz), n, mode, k, param, cap, _ptr(p), _ptr(ix), _ptr(sc),
+                                              C.byref(m), C.byref(st)), m)
         return p[: m.value].copy(), ix[: m.value].copy(), sc[:n], st
 
     def outlier_filter_device(self, d_xyz, n: int, mode, k, param, cap: int = 0, d_xyz_out=None, d_index_out=None,
@@ -613,9 +613,8 @@ class Context:
         """icp_hip_outlier_filter_device: the cloud and the outputs (cap kept entries, n scores; any
         may be None, all None counts only) in device buffers. Returns (m, stats)."""
         m, st = C.c_int64(0), OutlierStats()
-        _check_voxel(lib().icp_hip_outlier_filter_device(self._h, _dptr(d_xyz), n, mode, k, param, cap, _dptr(d_xyz_out),
-                                                         _dptr(d_index_out), _dptr(d_score_out), C.byref(m),
-                                                         C.byref(st)), m)
+        _check_m(lib().icp_hip_outlier_filter_device(self._h, _dptr(d_xyz), n, mode, k, param, cap, _dptr(d_xyz_out),
+                                                     _dptr(d_index_out), _dptr(d_score_out), C.byref(m), C.byref(st)), m)
         return m.value, st
 
     def outlier_last_timing(self) -> np.ndarray:
@@ -801,12 +800,17 @@ def _origin3(origin):
     return None if origin is None else np.ascontiguousarray(origin, np.float64).reshape(3)
 
 
-def _check_voxel(rc: int, m) -> None:
-    """_check, the error carrying the number of voxels the call reported (0: none)."""
+def _check_m(rc: int, m) -> None:
+    """_check, the error carrying the number of entries (voxels, kept points) the call reported (0: none)."""
     if rc != 0:
         e = IcpError(rc, lib().icp_hip_last_error().decode(errors="replace"))
         e.m = m.value
         raise e
+
+
+def _kept(cap: int, *dtypes):
+    """A compacting call's outputs of capacity cap (never empty): the (cap, 3) cloud, then one array per dtype."""
+    return (np.empty((max(cap, 1), 3)), *(np.empty(max(cap, 1), t) for t in dtypes))
 
 
 def voxel_downsample(xyz, voxel, origin=None, mode=VOXEL_CENTROID, cap=None, count_only=False):
@@ -821,10 +825,10 @@ def voxel_downsample(xyz, voxel, origin=None, mode=VOXEL_CENTROID, cap=None, cou
         m = lib().icp_voxel_downsample(_ptr(xyz), n, voxel, _ptr(o_in), mode, 0, None, None, None, _ptr(o_out))
         _check(min(m, 0))
         return m, o_out
-    p, f, k = np.empty((max(cap, 1), 3)), np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32)
+    p, f, k = _kept(cap, np.int32, np.int32)
     m = lib().icp_voxel_downsample(_ptr(xyz), n, voxel, _ptr(o_in), mode, cap, _ptr(p), _ptr(f), _ptr(k), _ptr(o_out))
     _check(min(m, 0))
-    return p[:m].copy(), f[:m].copy(), k[:m].copy(), o_out
+    return *(a[:m].copy() for a in (p, f, k)), o_out
 
 
 def outlier_filter(xyz, mode, k, param, cap=None, device: int = 0):

@@ -113,6 +113,20 @@ int check_device_ptr(const icp_hip_ctx* c, const void* p, const char* what, unsi
   return ICP_HIP_OK;
 }
 
+int check_optional_device_ptr(const icp_hip_ctx* c, const void* p, const char* what, unsigned align) {
+  return p ? check_device_ptr(c, p, what, align) : ICP_HIP_OK;
+}
+
+int fail_octree_build(int rc, const std::string& why) {
+  return fail(rc == 1 ? ICP_HIP_EINVAL : rc == -2 ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, why);
+}
+
+int last_timing(bool timed, const double* src, int count, const char* none_text, double* ms) {
+  if (!timed) return fail(ICP_HIP_ENOTREADY, none_text);
+  std::memcpy(ms, src, sizeof(double) * (size_t)count);
+  return ICP_HIP_OK;
+}
+
 // set_target after the argument checks, from a host cloud (xyz) or a device cloud (d_in), one of
 // them null. The device builder reads d_in in place; the host builder gets it staged down.
 // Whole or not at all: a failure leaves the context without a target (as free_target leaves it);
@@ -130,14 +144,12 @@ static int set_target_core(icp_hip_ctx* c, const double* xyz, const double* d_in
     // device build straight from the AoS cloud in HBM (octree_gpu.hip): the caller's, or the upload
     DevScratch S;  // the upload: released with this block, before the boxes and tables are made
     double* d_xyz = nullptr;
-    if (!d_in) {
-      HIP_TRY(S.alloc(&d_xyz, 3 * (size_t)n));
-      HIP_TRY(hipMemcpyAsync(d_xyz, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    }
-    GpuOctree t;
+    if (!d_in) HIP_TRY(call_upload(S, &d_xyz, xyz, 3 * (size_t)n, c->stream));
+    ScopedOctree oct;
     std::string why;
-    const int rc = gpu_build_octree(d_in ? d_in : d_xyz, n, max_points, max_depth, c->stream, &t, &why);
-    if (rc != 0) return fail(rc == 1 ? ICP_HIP_EINVAL : rc == -2 ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, why);
+    if (const int rc = gpu_build_octree(d_in ? d_in : d_xyz, n, max_points, max_depth, c->stream, &oct.t, &why))
+      return fail_octree_build(rc, why);
+    const GpuOctree t = oct.release();  // into the context (free_target)
     c->nodes = t.nodes;
     c->pts = t.pts;
     keep_tree_info(c, t, t.n_nodes);
@@ -196,6 +208,82 @@ static int set_target_core(icp_hip_ctx* c, const double* xyz, const double* d_in
   c->wc_gen++;  // cached candidate lists name points of the previous tree
   c->have_results = false;
   undo.dismiss();
+  return ICP_HIP_OK;
+}
+
+// get_correspondences after the argument checks, into host buffers or the caller's device buffers.
+static int corr_core(icp_hip_ctx* c, bool to_host, int32_t* idx_out, double* dist_out) {
+  if (!c->have_results) return fail(ICP_HIP_ENOTREADY, "no iteration has run on this source");
+  if (c->n_src == 0 || (!idx_out && !dist_out)) return ICP_HIP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  DevScratch S;
+  CallOut<int32_t> idx(idx_out, to_host);
+  CallOut<double> dist(dist_out, to_host);
+  HIP_TRY(idx.prepare(S, c->n_src));
+  HIP_TRY(dist.prepare(S, c->n_src));
+  HIP_TRY(launch_scatter_corr(c->perm, c->pos, c->pts, idx.dev(), c->dist, dist.dev(), c->n_src, c->stream));
+  HIP_TRY(idx.download(c->n_src, c->stream));
+  HIP_TRY(dist.download(c->n_src, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ICP_HIP_OK;
+}
+
+// nn after the argument checks. to_host: q and the outputs are host buffers (uploaded, searched,
+// downloaded); otherwise they are the caller's device buffers, read and written in place.
+static int nn_core(icp_hip_ctx* c, bool to_host, const double* q, int64_t n, int32_t* idx_out, double* dist_out) {
+  // the wave search addresses per-query arrays by 32-bit byte offsets (nn_device.h qat): launches
+  // of fewer than 2^29 queries, so larger sets go in slices (the answers are per query)
+  constexpr int64_t kSlice = (int64_t)1 << 28;
+  if (n > kSlice) {
+    PublishedLists lists{0, 0, 0};
+    for (int64_t off = 0; off < n; off += kSlice) {
+      const int64_t m = n - off < kSlice ? n - off : kSlice;
+      const int rc = nn_core(c, to_host, q + 3 * off, m, idx_out ? idx_out + off : nullptr, dist_out ? dist_out + off : nullptr);
+      if (rc != ICP_HIP_OK) return rc;
+      lists.exact += c->follow.last.exact;
+      lists.ball += c->follow.last.ball;
+      lists.lane += c->follow.last.lane;
+    }
+    c->follow.last = lists;
+    return ICP_HIP_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  FollowCounts counts{};  // before its source's owner: outlives the copy
+  DevScratch S;           // the host form's upload and outputs, the query arrays, the follow-up lists
+  CallOut<int32_t> idx(idx_out, to_host);
+  CallOut<double> dist(dist_out, to_host);
+  double *up = nullptr, *x = nullptr, *y = nullptr, *z = nullptr, *d = nullptr, *fbu = nullptr;
+  int32_t *pos = nullptr, *fbl = nullptr;
+  if (to_host) HIP_TRY(call_upload(S, &up, q, 3 * (size_t)n, c->stream));
+  HIP_TRY(S.alloc(&x, n));
+  HIP_TRY(S.alloc(&y, n));
+  HIP_TRY(S.alloc(&z, n));
+  HIP_TRY(S.alloc(&d, n));
+  HIP_TRY(S.alloc(&pos, n));
+  HIP_TRY(idx.prepare(S, n));
+  HIP_TRY(dist.prepare(S, n));
+  HIP_TRY(launch_deinterleave(to_host ? up : q, x, y, z, n, c->stream));
+  HIP_TRY(S.alloc(&fbl, (size_t)follow_list_ints(n)));
+  HIP_TRY(S.alloc(&fbu, (size_t)n));
+  NNLaunch a = base_launch(c);
+  a.x = x;
+  a.y = y;
+  a.z = z;
+  a.pos_out = pos;
+  a.dist_out = d;
+  a.n = n;
+  a.follow = carve_follow_lists(fbl, fbu, c->follow.counts, n, c->cfg.overflow_halves != 0,
+                                c->cfg.scan32 && c->cfg.wide_pass != 1);
+  HIP_TRY(c->follow.begin_search(c->stream));
+  HIP_TRY(launch_nn(a, c->stream));
+  HIP_TRY(hipMemcpyAsync(&counts, c->follow.counts, sizeof(FollowCounts), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->follow.last = published_lists(counts);
+  if (idx.dev() || dist.dev())  // either may be null
+    HIP_TRY(launch_scatter_corr(nullptr, pos, c->pts, idx.dev(), d, dist.dev(), n, c->stream));
+  HIP_TRY(idx.download(n, c->stream));
+  HIP_TRY(dist.download(n, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return ICP_HIP_OK;
 }
 
@@ -393,8 +481,7 @@ static int set_source_core(icp_hip_ctx* c, const double* xyz, const double* d_in
     const double* aos = d_in;
     if (!d_in) {
       double* up = nullptr;
-      HIP_TRY(S.alloc(&up, 3 * (size_t)n));
-      HIP_TRY(hipMemcpyAsync(up, xyz, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(call_upload(S, &up, xyz, 3 * (size_t)n, c->stream));
       aos = up;
     }
     if (c->cfg.query_order == 0) {
@@ -491,105 +578,22 @@ int icp_hip_get_source_device(icp_hip_ctx* c, double* d_xyz_out) {
 int icp_hip_get_correspondences(icp_hip_ctx* c, int32_t* idx_out, double* dist_out) {
   if (!c) return fail(ICP_HIP_EINVAL, "null argument");
   if (c->group) return group_get_correspondences(c, idx_out, dist_out);
-  if (!c->have_results) return fail(ICP_HIP_ENOTREADY, "no iteration has run on this source");
-  if (c->n_src == 0) return ICP_HIP_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  DevScratch S;
-  int32_t* di = nullptr;
-  double* dd = nullptr;
-  if (idx_out) HIP_TRY(S.alloc(&di, c->n_src));
-  if (dist_out) HIP_TRY(S.alloc(&dd, c->n_src));
-  HIP_TRY(launch_scatter_corr(c->perm, c->pos, c->pts, di, c->dist, dd, c->n_src, c->stream));
-  if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out, di, sizeof(int32_t) * c->n_src, hipMemcpyDeviceToHost, c->stream));
-  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd, sizeof(double) * c->n_src, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ICP_HIP_OK;
+  return corr_core(c, true, idx_out, dist_out);
 }
 
 int icp_hip_get_correspondences_device(icp_hip_ctx* c, int32_t* d_idx_out, double* d_dist_out) {
   if (!c) return fail(ICP_HIP_EINVAL, "null argument");
-  if (d_idx_out)  // int32 indices: 4-byte aligned
-    if (const int rc = check_device_ptr(c, d_idx_out, "get_correspondences_device", 4)) return rc;
-  if (d_dist_out)
-    if (const int rc = check_device_ptr(c, d_dist_out, "get_correspondences_device")) return rc;
+  // int32 indices: 4-byte aligned
+  if (const int rc = check_optional_device_ptr(c, d_idx_out, "get_correspondences_device", 4)) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_dist_out, "get_correspondences_device")) return rc;
   if (c->group) {
     const size_t n = (size_t)group_n_src(c);
-    std::vector<int32_t> idx(d_idx_out ? n : 0);
-    std::vector<double> d(d_dist_out ? n : 0);
-    const int rc = group_get_correspondences(c, d_idx_out ? idx.data() : nullptr, d_dist_out ? d.data() : nullptr);
-    if (rc != ICP_HIP_OK) return rc;
-    HIP_TRY(stage_up(c, d_idx_out, idx));
-    HIP_TRY(stage_up(c, d_dist_out, d));
-    return ICP_HIP_OK;
+    RelayOut<int32_t> idx(d_idx_out, n);
+    RelayOut<double> d(d_dist_out, n);
+    if (const int rc = group_get_correspondences(c, idx.host(), d.host())) return rc;
+    return relay_up(c, idx, d);
   }
-  if (!c->have_results) return fail(ICP_HIP_ENOTREADY, "no iteration has run on this source");
-  if (c->n_src == 0 || (!d_idx_out && !d_dist_out)) return ICP_HIP_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(launch_scatter_corr(c->perm, c->pos, c->pts, d_idx_out, c->dist, d_dist_out, c->n_src, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ICP_HIP_OK;
-}
-
-// nn after the argument checks. dev = false: q and the outputs are host buffers (uploaded, searched,
-// downloaded); dev = true: they are the caller's device buffers, read and written in place.
-static int nn_core(icp_hip_ctx* c, bool dev, const double* q, int64_t n, int32_t* idx_out, double* dist_out) {
-  // the wave search addresses per-query arrays by 32-bit byte offsets (nn_device.h qat): launches
-  // of fewer than 2^29 queries, so larger sets go in slices (the answers are per query)
-  constexpr int64_t kSlice = (int64_t)1 << 28;
-  if (n > kSlice) {
-    PublishedLists lists{0, 0, 0};
-    for (int64_t off = 0; off < n; off += kSlice) {
-      const int64_t m = n - off < kSlice ? n - off : kSlice;
-      const int rc = nn_core(c, dev, q + 3 * off, m, idx_out ? idx_out + off : nullptr, dist_out ? dist_out + off : nullptr);
-      if (rc != ICP_HIP_OK) return rc;
-      lists.exact += c->follow.last.exact;
-      lists.ball += c->follow.last.ball;
-      lists.lane += c->follow.last.lane;
-    }
-    c->follow.last = lists;
-    return ICP_HIP_OK;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  FollowCounts counts{};  // before its source's owner: outlives the copy
-  DevScratch S;           // the host variant's upload and outputs, the query arrays, the follow-up lists
-  double *up = nullptr, *x = nullptr, *y = nullptr, *z = nullptr, *d = nullptr, *dd = nullptr, *fbu = nullptr;
-  int32_t *pos = nullptr, *di = nullptr, *fbl = nullptr;
-  if (!dev) HIP_TRY(S.alloc(&up, 3 * (size_t)n));
-  HIP_TRY(S.alloc(&x, n));
-  HIP_TRY(S.alloc(&y, n));
-  HIP_TRY(S.alloc(&z, n));
-  HIP_TRY(S.alloc(&d, n));
-  if (!dev) HIP_TRY(S.alloc(&dd, n));
-  HIP_TRY(S.alloc(&pos, n));
-  if (!dev) HIP_TRY(S.alloc(&di, n));
-  if (!dev) HIP_TRY(hipMemcpyAsync(up, q, 3 * sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(launch_deinterleave(dev ? q : up, x, y, z, n, c->stream));
-  HIP_TRY(S.alloc(&fbl, (size_t)follow_list_ints(n)));
-  HIP_TRY(S.alloc(&fbu, (size_t)n));
-  NNLaunch a = base_launch(c);
-  a.x = x;
-  a.y = y;
-  a.z = z;
-  a.pos_out = pos;
-  a.dist_out = d;
-  a.n = n;
-  a.follow = carve_follow_lists(fbl, fbu, c->follow.counts, n, c->cfg.overflow_halves != 0,
-                                c->cfg.scan32 && c->cfg.wide_pass != 1);
-  HIP_TRY(c->follow.begin_search(c->stream));
-  HIP_TRY(launch_nn(a, c->stream));
-  HIP_TRY(hipMemcpyAsync(&counts, c->follow.counts, sizeof(FollowCounts), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->follow.last = published_lists(counts);
-  if (dev) {
-    // straight into the caller's buffers (either may be null)
-    if (idx_out || dist_out) HIP_TRY(launch_scatter_corr(nullptr, pos, c->pts, idx_out, d, dist_out, n, c->stream));
-  } else {
-    HIP_TRY(launch_scatter_corr(nullptr, pos, c->pts, di, d, dd, n, c->stream));
-    if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out, di, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-    if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ICP_HIP_OK;
+  return corr_core(c, false, d_idx_out, d_dist_out);
 }
 
 int icp_hip_nn(icp_hip_ctx* c, const double* q, int64_t n, int32_t* idx_out, double* dist_out) {
@@ -597,30 +601,25 @@ int icp_hip_nn(icp_hip_ctx* c, const double* q, int64_t n, int32_t* idx_out, dou
   if (c->group) return icp_hip_nn(group_member(c, 0), q, n, idx_out, dist_out);  // the replicated octree
   if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
   if (n == 0) return ICP_HIP_OK;
-  return nn_core(c, false, q, n, idx_out, dist_out);
+  return nn_core(c, true, q, n, idx_out, dist_out);
 }
 
 int icp_hip_nn_device(icp_hip_ctx* c, const double* d_q, int64_t n, int32_t* d_idx_out, double* d_dist_out) {
   if (!c || n < 0) return fail(ICP_HIP_EINVAL, "bad arguments");
   if (const int rc = check_device_ptr(c, d_q, "nn_device")) return rc;
-  if (d_idx_out)
-    if (const int rc = check_device_ptr(c, d_idx_out, "nn_device", 4)) return rc;
-  if (d_dist_out)
-    if (const int rc = check_device_ptr(c, d_dist_out, "nn_device")) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_idx_out, "nn_device", 4)) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_dist_out, "nn_device")) return rc;
   if (c->group) {  // the first member's replica, through host memory (the buffers may be another device's)
     std::vector<double> hq;
     HIP_TRY(stage_down(c, &hq, d_q, 3 * (size_t)n));
-    std::vector<int32_t> idx(d_idx_out ? (size_t)n : 0);
-    std::vector<double> d(d_dist_out ? (size_t)n : 0);
-    const int rc = icp_hip_nn(group_member(c, 0), hq.data(), n, d_idx_out ? idx.data() : nullptr, d_dist_out ? d.data() : nullptr);
-    if (rc != ICP_HIP_OK) return rc;
-    HIP_TRY(stage_up(c, d_idx_out, idx));
-    HIP_TRY(stage_up(c, d_dist_out, d));
-    return ICP_HIP_OK;
+    RelayOut<int32_t> idx(d_idx_out, (size_t)n);
+    RelayOut<double> d(d_dist_out, (size_t)n);
+    if (const int rc = icp_hip_nn(group_member(c, 0), hq.data(), n, idx.host(), d.host())) return rc;
+    return relay_up(c, idx, d);
   }
   if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
   if (n == 0) return ICP_HIP_OK;
-  return nn_core(c, true, d_q, n, d_idx_out, d_dist_out);
+  return nn_core(c, false, d_q, n, d_idx_out, d_dist_out);
 }
 
 int icp_hip_traversal_counts(icp_hip_ctx* c, double* mean_entries, double* mean_points) {

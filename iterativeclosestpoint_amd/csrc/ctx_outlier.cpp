@@ -1,7 +1,7 @@
 // ctx_outlier.cpp — the context side of outlier removal: the argument checks, the
 // call's private octree and scratch, the phases of outlier_kernels.hip on the context's stream with
-// the two small read-backs between them, and the host and device variants around that core. It
-// reads no target or source of the context and changes none.
+// the two small read-backs between them, and the host, device and group forms around that core
+// (§3.8). It reads no target or source of the context and changes none.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -20,19 +20,7 @@ namespace {
 constexpr int kOutlierLeafPoints = 10;
 constexpr int kOutlierMaxDepth = 20;
 
-// The private octree's two device arrays, freed on every way out of the call.
-struct ScopedOctree {
-  GpuOctree t;
-  ScopedOctree() = default;
-  ScopedOctree(const ScopedOctree&) = delete;
-  ScopedOctree& operator=(const ScopedOctree&) = delete;
-  ~ScopedOctree() {
-    if (t.nodes) (void)hipFree(t.nodes);
-    if (t.pts) (void)hipFree(t.pts);
-  }
-};
-
-std::string cap_text(int64_t m, int64_t cap) {
+std::string outlier_cap_text(int64_t m, int64_t cap) {
   return "outlier_filter: " + std::to_string(m) + " points kept, the outputs' capacity is " + std::to_string(cap);
 }
 
@@ -55,9 +43,9 @@ int outlier_args(icp_hip_ctx* c, const double* xyz, int64_t n, int mode, int k, 
   return ICP_HIP_OK;
 }
 
-// The call after the argument checks. d_xyz is device memory. The outputs are the caller's device
-// buffers (to_host false) or host buffers that get the first m entries of scratch ones.
-int outlier_core(icp_hip_ctx* c, const double* d_xyz, int64_t n, int mode, int k, double param, int64_t cap,
+// The call after the argument checks, in its host form (to_host: the cloud is uploaded, the outputs
+// get the first m entries of scratch buffers) or on the caller's device buffers.
+int outlier_core(icp_hip_ctx* c, const double* xyz_in, int64_t n, int mode, int k, double param, int64_t cap,
                  bool to_host, double* xyz_out, int32_t* index_out, double* score_out, int64_t* m_out,
                  icp_outlier_stats* stats) {
   OutlierHead hd;  // before the scratch: outlives the copies into it
@@ -67,12 +55,17 @@ int outlier_core(icp_hip_ctx* c, const double* d_xyz, int64_t n, int mode, int k
   PhaseEvents<5> ev;  // build, scores, statistics, flags + sum, gather
   ScopedOctree oct;
   DevScratch S;
+  double* up = nullptr;
+  if (to_host) HIP_TRY(call_upload(S, &up, xyz_in, 3 * (size_t)n, s));
+  const double* d_xyz = to_host ? up : xyz_in;
+  CallOut<double> xyz(xyz_out, to_host), scores(score_out, to_host);
+  CallOut<int32_t> index(index_out, to_host);
 
   HIP_TRY(ev.mark(0, s));
   {
     std::string why;
-    const int rc = gpu_build_octree(d_xyz, n, kOutlierLeafPoints, kOutlierMaxDepth, s, &oct.t, &why);
-    if (rc != 0) return fail(rc == 1 ? ICP_HIP_EINVAL : rc == -2 ? ICP_HIP_ENOMEM : ICP_HIP_EDEVICE, why);
+    if (const int rc = gpu_build_octree(d_xyz, n, kOutlierLeafPoints, kOutlierMaxDepth, s, &oct.t, &why))
+      return fail_octree_build(rc, why);
   }
   HIP_TRY(ev.mark(1, s));
   const int levels = oct.t.max_inner_depth + 1 > 0 ? oct.t.max_inner_depth + 1 : 1;
@@ -106,28 +99,19 @@ int outlier_core(icp_hip_ctx* c, const double* d_xyz, int64_t n, int mode, int k
   HIP_TRY(hipMemcpyAsync(&hd, head, sizeof(hd), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));  // m: the capacity check needs it
   const int64_t m = hd.m;
-  *m_out = m;
   const bool any_kept = xyz_out || index_out;
-  if (any_kept && m > cap) return fail(ICP_HIP_EINVAL, cap_text(m, cap));
+  if (const int rc = report_m(m, cap, any_kept, outlier_cap_text, m_out)) return rc;
 
   if (any_kept) {
-    double* dx = xyz_out;
-    int32_t* di = index_out;
-    if (to_host) {
-      if (xyz_out) HIP_TRY(S.alloc(&dx, 3 * (size_t)m));
-      if (index_out) HIP_TRY(S.alloc(&di, (size_t)m));
-    }
+    HIP_TRY(xyz.prepare(S, 3 * (size_t)m));
+    HIP_TRY(index.prepare(S, (size_t)m));
     HIP_TRY(ev.mark(8, s));
-    HIP_TRY(launch_outlier_gather(d_xyz, n, flag, pos, dx, di, s));
+    HIP_TRY(launch_outlier_gather(d_xyz, n, flag, pos, xyz.dev(), index.dev(), s));
     HIP_TRY(ev.mark(9, s));
-    if (to_host) {
-      if (xyz_out) HIP_TRY(hipMemcpyAsync(xyz_out, dx, 3 * sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
-      if (index_out) HIP_TRY(hipMemcpyAsync(index_out, di, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
-    }
+    HIP_TRY(xyz.download(3 * (size_t)m, s));
+    HIP_TRY(index.download((size_t)m, s));
   }
-  if (score_out)
-    HIP_TRY(hipMemcpyAsync(score_out, score, sizeof(double) * (size_t)n,
-                           to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+  HIP_TRY(scores.copy_from(score, (size_t)n, s));  // the scores feed the later phases: always the call's own buffer
   HIP_TRY(hipStreamSynchronize(s));
   if (stats) {
     stats->n = n;
@@ -155,58 +139,41 @@ int icp_hip_outlier_filter(icp_hip_ctx* c, const double* xyz, int64_t n, int mod
   if (c->group)
     return icp_hip_outlier_filter(group_member(c, 0), xyz, n, mode, k, param, cap, xyz_out, index_out, score_out, m_out,
                                   stats);
-  HIP_TRY(hipSetDevice(c->device));
-  DevScratch S;
-  double* up = nullptr;
-  HIP_TRY(S.alloc(&up, 3 * (size_t)n));
-  HIP_TRY(hipMemcpyAsync(up, xyz, 3 * sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  return outlier_core(c, up, n, mode, k, param, cap, true, xyz_out, index_out, score_out, m_out, stats);
+  return outlier_core(c, xyz, n, mode, k, param, cap, true, xyz_out, index_out, score_out, m_out, stats);
 }
 
 int icp_hip_outlier_filter_device(icp_hip_ctx* c, const double* d_xyz, int64_t n, int mode, int k, double param,
                                   int64_t cap, double* d_xyz_out, int32_t* d_index_out, double* d_score_out,
                                   int64_t* m_out, icp_outlier_stats* stats) {
+  const char* what = "outlier_filter_device";
   if (!c || !m_out) return fail(ICP_HIP_EINVAL, "outlier_filter_device: null argument");
   *m_out = 0;
-  if (const int rc = check_device_ptr(c, d_xyz, "outlier_filter_device")) return rc;
-  if (d_xyz_out)
-    if (const int rc = check_device_ptr(c, d_xyz_out, "outlier_filter_device")) return rc;
-  if (d_index_out)
-    if (const int rc = check_device_ptr(c, d_index_out, "outlier_filter_device", 4)) return rc;
-  if (d_score_out)
-    if (const int rc = check_device_ptr(c, d_score_out, "outlier_filter_device")) return rc;
+  if (const int rc = check_device_ptr(c, d_xyz, what)) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_xyz_out, what)) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_index_out, what, 4)) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_score_out, what)) return rc;
   if (const int rc = outlier_args(c, d_xyz, n, mode, k, param, m_out)) return rc;
-  if (c->group) {  // the first member, through host memory (the buffers may be another device's)
-    std::vector<double> h;
-    HIP_TRY(stage_down(c, &h, d_xyz, 3 * (size_t)n));
-    std::vector<double> sc(d_score_out ? (size_t)n : 0);
-    int64_t m = 0;
-    int rc = icp_hip_outlier_filter(group_member(c, 0), h.data(), n, mode, k, param, 0, nullptr, nullptr,
-                                    d_score_out ? sc.data() : nullptr, &m, stats);
-    *m_out = m;
-    if (rc != ICP_HIP_OK) return rc;
-    if ((d_xyz_out || d_index_out) && m > cap) return fail(ICP_HIP_EINVAL, cap_text(m, cap));
-    std::vector<double> p(d_xyz_out ? 3 * (size_t)m : 0);
-    std::vector<int32_t> ix(d_index_out ? (size_t)m : 0);
-    if (d_xyz_out || d_index_out) {
-      rc = icp_hip_outlier_filter(group_member(c, 0), h.data(), n, mode, k, param, m, d_xyz_out ? p.data() : nullptr,
-                                  d_index_out ? ix.data() : nullptr, nullptr, &m, stats);
-      if (rc != ICP_HIP_OK) return rc;
-    }
-    HIP_TRY(stage_up(c, d_xyz_out, p));
-    HIP_TRY(stage_up(c, d_index_out, ix));
-    HIP_TRY(stage_up(c, d_score_out, sc));
-    return ICP_HIP_OK;
-  }
-  return outlier_core(c, d_xyz, n, mode, k, param, cap, false, d_xyz_out, d_index_out, d_score_out, m_out, stats);
+  if (!c->group)
+    return outlier_core(c, d_xyz, n, mode, k, param, cap, false, d_xyz_out, d_index_out, d_score_out, m_out, stats);
+  // the first member, through host memory (the buffers may be another device's)
+  std::vector<double> h;
+  HIP_TRY(stage_down(c, &h, d_xyz, 3 * (size_t)n));
+  RelayOut<double> p(d_xyz_out), sc(d_score_out, (size_t)n);
+  RelayOut<int32_t> ix(d_index_out);
+  const int rc = relay_count_then_fill(  // the counting call fetches the scores and the statistics too
+      d_xyz_out || d_index_out, cap, outlier_cap_text, m_out, [&](bool fill, int64_t mcap, int64_t* m) {
+        if (fill) p.resize(3 * (size_t)mcap), ix.resize((size_t)mcap);
+        return icp_hip_outlier_filter(group_member(c, 0), h.data(), n, mode, k, param, mcap, p.host(), ix.host(),
+                                      fill ? nullptr : sc.host(), m, stats);
+      });
+  if (rc != ICP_HIP_OK) return rc;
+  return relay_up(c, p, ix, sc);
 }
 
 int icp_hip_outlier_last_timing(icp_hip_ctx* c, double ms[4]) {
   if (!c || !ms) return fail(ICP_HIP_EINVAL, "null argument");
-  if (c->group) return icp_hip_outlier_last_timing(group_member(c, 0), ms);
-  if (!c->outlier_timed) return fail(ICP_HIP_ENOTREADY, "no outlier call has run on this context");
-  std::memcpy(ms, c->outlier_ms, sizeof(c->outlier_ms));
-  return ICP_HIP_OK;
+  if (c->group) c = group_member(c, 0);
+  return last_timing(c->outlier_timed, c->outlier_ms, 4, "no outlier call has run on this context", ms);
 }
 
 }  // extern "C"

@@ -33,32 +33,27 @@ int knn_check(const icp_hip_ctx* c, int k) {
   return ICP_HIP_OK;
 }
 
-// knn after the argument checks; dev: q and the outputs are the caller's device buffers.
-int knn_core(icp_hip_ctx* c, bool dev, const double* q, int64_t n, int k, int32_t* idx_out, double* d2_out) {
+// knn after the argument checks. to_host: q and the outputs are host buffers, a slice at a time
+// through the scratch; otherwise they are the caller's device buffers.
+int knn_core(icp_hip_ctx* c, bool to_host, const double* q, int64_t n, int k, int32_t* idx_out, double* d2_out) {
   HIP_TRY(hipSetDevice(c->device));
-  if (dev) {
-    for (int64_t off = 0; off < n; off += kKnnSlice) {
-      const int64_t m = std::min(n - off, kKnnSlice);
-      HIP_TRY(launch_knn(c->nodes, c->pts, c->levels, q + 3 * off, m, k, idx_out ? idx_out + off * k : nullptr,
-                         d2_out ? d2_out + off * k : nullptr, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return ICP_HIP_OK;
-  }
   const int64_t cap = std::min(n, kKnnSlice);
   DevScratch S;
-  double *dq = nullptr, *dd = nullptr;
-  int32_t* di = nullptr;
-  HIP_TRY(S.alloc(&dq, 3 * (size_t)cap));
-  if (idx_out) HIP_TRY(S.alloc(&di, (size_t)cap * k));
-  if (d2_out) HIP_TRY(S.alloc(&dd, (size_t)cap * k));
+  CallOut<int32_t> idx(idx_out, to_host);
+  CallOut<double> d2(d2_out, to_host);
+  double* up = nullptr;
+  if (to_host) HIP_TRY(S.alloc(&up, 3 * (size_t)cap));
+  HIP_TRY(idx.prepare(S, (size_t)cap * k));
+  HIP_TRY(d2.prepare(S, (size_t)cap * k));
   for (int64_t off = 0; off < n; off += kKnnSlice) {
     const int64_t m = std::min(n - off, kKnnSlice);
-    HIP_TRY(hipMemcpyAsync(dq, q + 3 * off, 3 * sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch_knn(c->nodes, c->pts, c->levels, dq, m, k, di, dd, c->stream));
-    if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out + off * k, di, sizeof(int32_t) * m * k, hipMemcpyDeviceToHost, c->stream));
-    if (d2_out) HIP_TRY(hipMemcpyAsync(d2_out + off * k, dd, sizeof(double) * m * k, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (to_host) HIP_TRY(hipMemcpyAsync(up, q + 3 * off, 3 * sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_knn(c->nodes, c->pts, c->levels, to_host ? up : q + 3 * off, m, k, idx.dev((size_t)off * k),
+                       d2.dev((size_t)off * k), c->stream));
+    HIP_TRY(idx.download((size_t)m * k, c->stream, (size_t)off * k));
+    HIP_TRY(d2.download((size_t)m * k, c->stream, (size_t)off * k));
+    // the host form's scratch is the next slice's too; the device form waits once, for all slices
+    if (to_host || off + m == n) HIP_TRY(hipStreamSynchronize(c->stream));
   }
   return ICP_HIP_OK;
 }
@@ -92,32 +87,26 @@ int icp_hip_knn(icp_hip_ctx* c, const double* q, int64_t n, int k, int32_t* idx_
   if (c->group) return icp_hip_knn(group_member(c, 0), q, n, k, idx_out, d2_out);  // the replicated octree
   if (const int rc = knn_check(c, k)) return rc;
   if (n == 0 || (!idx_out && !d2_out)) return ICP_HIP_OK;
-  return knn_core(c, false, q, n, k, idx_out, d2_out);
+  return knn_core(c, true, q, n, k, idx_out, d2_out);
 }
 
 int icp_hip_knn_device(icp_hip_ctx* c, const double* d_q, int64_t n, int k, int32_t* d_idx_out, double* d_d2_out) {
   if (!c || n < 0) return fail(ICP_HIP_EINVAL, "bad arguments");
   if (const int rc = check_device_ptr(c, d_q, "knn_device")) return rc;
-  if (d_idx_out)
-    if (const int rc = check_device_ptr(c, d_idx_out, "knn_device", 4)) return rc;
-  if (d_d2_out)
-    if (const int rc = check_device_ptr(c, d_d2_out, "knn_device")) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_idx_out, "knn_device", 4)) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_d2_out, "knn_device")) return rc;
   if (c->group) {  // the first member's replica, through host memory (the buffers may be another device's)
     if (const int rc = knn_k_check(k)) return rc;
     std::vector<double> hq;
-    std::vector<int32_t> idx(d_idx_out ? (size_t)n * k : 0);
-    std::vector<double> d(d_d2_out ? (size_t)n * k : 0);
+    RelayOut<int32_t> idx(d_idx_out, (size_t)n * k);
+    RelayOut<double> d(d_d2_out, (size_t)n * k);
     HIP_TRY(stage_down(c, &hq, d_q, 3 * (size_t)n));
-    const int rc = icp_hip_knn(group_member(c, 0), hq.data(), n, k, d_idx_out ? idx.data() : nullptr,
-                               d_d2_out ? d.data() : nullptr);
-    if (rc != ICP_HIP_OK) return rc;
-    HIP_TRY(stage_up(c, d_idx_out, idx));
-    HIP_TRY(stage_up(c, d_d2_out, d));
-    return ICP_HIP_OK;
+    if (const int rc = icp_hip_knn(group_member(c, 0), hq.data(), n, k, idx.host(), d.host())) return rc;
+    return relay_up(c, idx, d);
   }
   if (const int rc = knn_check(c, k)) return rc;
   if (n == 0 || (!d_idx_out && !d_d2_out)) return ICP_HIP_OK;
-  return knn_core(c, true, d_q, n, k, d_idx_out, d_d2_out);
+  return knn_core(c, false, d_q, n, k, d_idx_out, d_d2_out);
 }
 
 int icp_hip_estimate_target_normals(icp_hip_ctx* c, int k, const double* viewpoint) {
@@ -147,8 +136,7 @@ int icp_hip_set_target_normals(icp_hip_ctx* c, const double* n_xyz) {
   HIP_TRY(hipSetDevice(c->device));
   DevScratch S;
   double* up = nullptr;
-  HIP_TRY(S.alloc(&up, 3 * (size_t)c->n_tgt));
-  HIP_TRY(hipMemcpyAsync(up, n_xyz, 3 * sizeof(double) * c->n_tgt, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(call_upload(S, &up, n_xyz, 3 * (size_t)c->n_tgt, c->stream));
   return set_normals_core(c, up);
 }
 

@@ -1,7 +1,7 @@
 // ctx_voxel.cpp — the context side of voxel-grid down-sampling: the argument
 // checks, the call's scratch, the five phases of voxel_kernels.hip on the context's stream with the
-// two small read-backs between them, and the host and device variants around that core. It reads
-// no target or source of the context and changes none.
+// two small read-backs between them, and the host, device and group forms around that core
+// (§3.8). It reads no target or source of the context and changes none.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -14,9 +14,9 @@ using namespace icp;
 
 namespace {
 
-// The call after the pointer checks. d_xyz is device memory. The outputs are the caller's device
-// buffers (to_host false) or host buffers that get the first m entries of scratch ones.
-int voxel_core(icp_hip_ctx* c, const double* d_xyz, int64_t n, double h, const double* origin, int mode, int64_t cap,
+// The call after the pointer checks, in its host form (to_host: the cloud is uploaded, the outputs
+// get the first m entries of scratch buffers) or on the caller's device buffers.
+int voxel_core(icp_hip_ctx* c, const double* xyz_in, int64_t n, double h, const double* origin, int mode, int64_t cap,
                bool to_host, double* xyz_out, int32_t* first_out, int32_t* count_out, int64_t* m_out,
                double origin_out[3]) {
   VoxelHead hd;  // before the scratch: outlives the copies into it
@@ -25,6 +25,11 @@ int voxel_core(icp_hip_ctx* c, const double* d_xyz, int64_t n, double h, const d
   hipStream_t s = c->stream;
   PhaseEvents<5> ev;  // bounds, keys, sort, runs, reduce
   DevScratch S;
+  double* up = nullptr;
+  if (to_host) HIP_TRY(call_upload(S, &up, xyz_in, 3 * (size_t)n, s));
+  const double* d_xyz = to_host ? up : xyz_in;
+  CallOut<double> xyz(xyz_out, to_host);
+  CallOut<int32_t> first(first_out, to_host), count(count_out, to_host);
   VoxelHead* head = nullptr;
   double* parts = nullptr;
   uint64_t *keys = nullptr, *keys_sorted = nullptr;
@@ -66,26 +71,19 @@ int voxel_core(icp_hip_ctx* c, const double* d_xyz, int64_t n, double h, const d
   HIP_TRY(hipMemcpyAsync(&hd, head, sizeof(hd), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));  // m: the capacity check needs it
   const int64_t m = hd.m;
-  *m_out = m;
   const bool any_out = xyz_out || first_out || count_out;
-  if (any_out && m > cap) return fail(ICP_HIP_EINVAL, voxel_cap_text(m, cap));
+  if (const int rc = report_m(m, cap, any_out, voxel_cap_text, m_out)) return rc;
 
   if (any_out) {
-    double* dx = xyz_out;
-    int32_t *df = first_out, *dc = count_out;
-    if (to_host) {
-      if (xyz_out) HIP_TRY(S.alloc(&dx, 3 * (size_t)m));
-      if (first_out) HIP_TRY(S.alloc(&df, (size_t)m));
-      if (count_out) HIP_TRY(S.alloc(&dc, (size_t)m));
-    }
+    HIP_TRY(xyz.prepare(S, 3 * (size_t)m));
+    HIP_TRY(first.prepare(S, (size_t)m));
+    HIP_TRY(count.prepare(S, (size_t)m));
     HIP_TRY(ev.mark(8, s));
-    HIP_TRY(launch_voxel_reduce(d_xyz, idx_sorted, starts, head, m, mode, dx, df, dc, s));
+    HIP_TRY(launch_voxel_reduce(d_xyz, idx_sorted, starts, head, m, mode, xyz.dev(), first.dev(), count.dev(), s));
     HIP_TRY(ev.mark(9, s));
-    if (to_host) {
-      if (xyz_out) HIP_TRY(hipMemcpyAsync(xyz_out, dx, 3 * sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
-      if (first_out) HIP_TRY(hipMemcpyAsync(first_out, df, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
-      if (count_out) HIP_TRY(hipMemcpyAsync(count_out, dc, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
-    }
+    HIP_TRY(xyz.download(3 * (size_t)m, s));
+    HIP_TRY(first.download((size_t)m, s));
+    HIP_TRY(count.download((size_t)m, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   HIP_TRY(ev.read(c->voxel_ms));
@@ -113,55 +111,41 @@ int icp_hip_voxel_downsample(icp_hip_ctx* c, const double* xyz, int64_t n, doubl
   if (c->group)
     return icp_hip_voxel_downsample(group_member(c, 0), xyz, n, voxel, origin, mode, cap, xyz_out, first_out, count_out,
                                     m_out, origin_out);
-  HIP_TRY(hipSetDevice(c->device));
-  DevScratch S;
-  double* up = nullptr;
-  HIP_TRY(S.alloc(&up, 3 * (size_t)n));
-  HIP_TRY(hipMemcpyAsync(up, xyz, 3 * sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  return voxel_core(c, up, n, voxel, origin, mode, cap, true, xyz_out, first_out, count_out, m_out, origin_out);
+  return voxel_core(c, xyz, n, voxel, origin, mode, cap, true, xyz_out, first_out, count_out, m_out, origin_out);
 }
 
 int icp_hip_voxel_downsample_device(icp_hip_ctx* c, const double* d_xyz, int64_t n, double voxel, const double* origin,
                                     int mode, int64_t cap, double* d_xyz_out, int32_t* d_first_out, int32_t* d_count_out,
                                     int64_t* m_out, double origin_out[3]) {
+  const char* what = "voxel_downsample_device";
   if (!c || !m_out) return fail(ICP_HIP_EINVAL, "voxel_downsample_device: null argument");
   *m_out = 0;
-  if (const int rc = check_device_ptr(c, d_xyz, "voxel_downsample_device")) return rc;
-  if (d_xyz_out)
-    if (const int rc = check_device_ptr(c, d_xyz_out, "voxel_downsample_device")) return rc;
-  if (d_first_out)
-    if (const int rc = check_device_ptr(c, d_first_out, "voxel_downsample_device", 4)) return rc;
-  if (d_count_out)
-    if (const int rc = check_device_ptr(c, d_count_out, "voxel_downsample_device", 4)) return rc;
+  if (const int rc = check_device_ptr(c, d_xyz, what)) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_xyz_out, what)) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_first_out, what, 4)) return rc;
+  if (const int rc = check_optional_device_ptr(c, d_count_out, what, 4)) return rc;
   if (const int rc = voxel_args(c, d_xyz, n, voxel, origin, mode, m_out)) return rc;
-  if (c->group) {  // the first member, through host memory (the buffers may be another device's)
-    std::vector<double> h;
-    HIP_TRY(stage_down(c, &h, d_xyz, 3 * (size_t)n));
-    int64_t m = 0;
-    int rc = icp_hip_voxel_downsample(group_member(c, 0), h.data(), n, voxel, origin, mode, 0, nullptr, nullptr, nullptr,
-                                      &m, origin_out);
-    *m_out = m;
-    if (rc != ICP_HIP_OK || (!d_xyz_out && !d_first_out && !d_count_out)) return rc;
-    if (m > cap) return fail(ICP_HIP_EINVAL, voxel_cap_text(m, cap));
-    std::vector<double> p(d_xyz_out ? 3 * (size_t)m : 0);
-    std::vector<int32_t> f(d_first_out ? (size_t)m : 0), k(d_count_out ? (size_t)m : 0);
-    rc = icp_hip_voxel_downsample(group_member(c, 0), h.data(), n, voxel, origin, mode, m, d_xyz_out ? p.data() : nullptr,
-                                  d_first_out ? f.data() : nullptr, d_count_out ? k.data() : nullptr, &m, origin_out);
-    if (rc != ICP_HIP_OK) return rc;
-    HIP_TRY(stage_up(c, d_xyz_out, p));
-    HIP_TRY(stage_up(c, d_first_out, f));
-    HIP_TRY(stage_up(c, d_count_out, k));
-    return ICP_HIP_OK;
-  }
-  return voxel_core(c, d_xyz, n, voxel, origin, mode, cap, false, d_xyz_out, d_first_out, d_count_out, m_out, origin_out);
+  if (!c->group)
+    return voxel_core(c, d_xyz, n, voxel, origin, mode, cap, false, d_xyz_out, d_first_out, d_count_out, m_out, origin_out);
+  // the first member, through host memory (the buffers may be another device's)
+  std::vector<double> h;
+  HIP_TRY(stage_down(c, &h, d_xyz, 3 * (size_t)n));
+  RelayOut<double> p(d_xyz_out);
+  RelayOut<int32_t> f(d_first_out), k(d_count_out);
+  const int rc = relay_count_then_fill(
+      d_xyz_out || d_first_out || d_count_out, cap, voxel_cap_text, m_out, [&](bool fill, int64_t mcap, int64_t* m) {
+        if (fill) p.resize(3 * (size_t)mcap), f.resize((size_t)mcap), k.resize((size_t)mcap);
+        return icp_hip_voxel_downsample(group_member(c, 0), h.data(), n, voxel, origin, mode, mcap, p.host(), f.host(),
+                                        k.host(), m, origin_out);
+      });
+  if (rc != ICP_HIP_OK) return rc;
+  return relay_up(c, p, f, k);
 }
 
 int icp_hip_voxel_last_timing(icp_hip_ctx* c, double ms[5]) {
   if (!c || !ms) return fail(ICP_HIP_EINVAL, "null argument");
-  if (c->group) return icp_hip_voxel_last_timing(group_member(c, 0), ms);
-  if (!c->voxel_timed) return fail(ICP_HIP_ENOTREADY, "no voxel call has run on this context");
-  std::memcpy(ms, c->voxel_ms, sizeof(c->voxel_ms));
-  return ICP_HIP_OK;
+  if (c->group) c = group_member(c, 0);
+  return last_timing(c->voxel_timed, c->voxel_ms, 5, "no voxel call has run on this context", ms);
 }
 
 }  // extern "C"

@@ -6,9 +6,11 @@
 
 #include <atomic>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "../../include/icp_hip.h"
+#include "call_io.h"
 #include "ctx_util.h"
 #include "kernels.h"
 
@@ -190,6 +192,10 @@ icp::NNLaunch base_launch(const icp_hip_ctx* c);
 // `what`) unless p is non-null, aligned, and device memory of the context's device or managed
 // memory by hipPointerGetAttributes. Never dereferences p.
 int check_device_ptr(const icp_hip_ctx* c, const void* p, const char* what, unsigned align = 8);
+// The same for an optional output: a null pointer is fine.
+int check_optional_device_ptr(const icp_hip_ctx* c, const void* p, const char* what, unsigned align = 8);
+// gpu_build_octree's return code (octree_gpu.h) and text as the C ABI's error.
+int fail_octree_build(int rc, const std::string& why);
 
 // The host-staged routes of the device variants: the caller's buffer through host memory, complete
 // at return. A group's buffer may be any device's, so it is copied without the member's stream.
@@ -208,6 +214,58 @@ hipError_t stage_up(const icp_hip_ctx* c, T* d, const std::vector<T>& h) {
   if (c->group) return hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
   hipError_t e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
   return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
+
+// A group's relay of one optional device output: the host vector that the first
+// member's host call fills, then staged up to the caller's buffer. Nothing when d is null.
+template <typename T>
+class RelayOut {
+ public:
+  explicit RelayOut(T* d, size_t count = 0) : d_(d), v_(d ? count : 0) {}
+  void resize(size_t count) { v_.resize(d_ ? count : 0); }
+  T* host() { return v_.empty() ? nullptr : v_.data(); }
+  hipError_t up(const icp_hip_ctx* c) const { return stage_up(c, d_, v_); }
+
+ private:
+  T* d_;
+  std::vector<T> v_;
+};
+
+// The relay's last step: every output staged up, stopping at the first failure.
+template <class... Outs>
+int relay_up(const icp_hip_ctx* c, const Outs&... outs) {
+  hipError_t e = hipSuccess;
+  ((e = e == hipSuccess ? outs.up(c) : e), ...);
+  return e == hipSuccess ? ICP_HIP_OK : fail_hip("stage_up", e);
+}
+
+// The text of a compacting call's "m entries do not fit the capacity" error.
+using CapText = std::string (*)(int64_t m, int64_t cap);
+
+// A compacting call once m is known: the caller gets it even when the kept outputs (any_kept: one
+// is asked for) then prove too small for it.
+inline int report_m(int64_t m, int64_t cap, bool any_kept, CapText cap_text, int64_t* m_out) {
+  *m_out = m;
+  return any_kept && m > cap ? fail(ICP_HIP_EINVAL, cap_text(m, cap)) : ICP_HIP_OK;
+}
+
+// A *_last_timing getter's body: the count phase times of the last call, or ICP_HIP_ENOTREADY with
+// none_text when none has run.
+int last_timing(bool timed, const double* src, int count, const char* none_text, double* ms);
+
+// A group's relay of a compacting call, whose outputs' size m is known only from the call itself:
+// call(false, 0, &m) is the member's host call with capacity 0 and no kept output (it counts, and
+// fetches what does not depend on m); call(true, m, &m) the one that fills kept outputs of m
+// entries, made only when one is asked for (any_kept) and m fits the caller's capacity. *m_out is
+// set even when the call then fails. The caller stages the outputs up (relay_up) after ICP_HIP_OK.
+template <class Call>
+int relay_count_then_fill(bool any_kept, int64_t cap, CapText cap_text, int64_t* m_out, Call call) {
+  int64_t m = 0;
+  const int rc = call(false, (int64_t)0, &m);
+  *m_out = m;
+  if (rc != ICP_HIP_OK || !any_kept) return rc;
+  if (const int rc2 = report_m(m, cap, true, cap_text, m_out)) return rc2;
+  return call(true, m, &m);
 }
 
 // --- ctx_prewalk.cpp

@@ -180,6 +180,11 @@ Args parse(int argc, char** argv) {
   return a;
 }
 
+void print_cloud(int64_t n, const icp_las_header& hdr) {
+  std::cout << "  " << n << " points, scale (" << hdr.scale[0] << ", " << hdr.scale[1] << ", " << hdr.scale[2]
+            << "), offset (" << hdr.offset[0] << ", " << hdr.offset[1] << ", " << hdr.offset[2] << ")" << std::endl;
+}
+
 bool read_cloud(const std::string& path, std::vector<double>& xyz, icp_las_header& hdr) {
   std::cout << "  reading " << path << std::endl;
   if (icp_las_read_header(path.c_str(), ICP_LAS_CLI, &hdr) != 0) return false;
@@ -187,8 +192,7 @@ bool read_cloud(const std::string& path, std::vector<double>& xyz, icp_las_heade
   const int64_t got = icp_las_read(path.c_str(), ICP_LAS_CLI, 0, xyz.data(), &hdr);
   if (got <= 0) return false;  // readLASFile returns read_count > 0 (:377)
   xyz.resize((size_t)got * 3);
-  std::cout << "  " << got << " points, scale (" << hdr.scale[0] << ", " << hdr.scale[1] << ", " << hdr.scale[2]
-            << "), offset (" << hdr.offset[0] << ", " << hdr.offset[1] << ", " << hdr.offset[2] << ")" << std::endl;
+  print_cloud(got, hdr);
   return true;
 }
 
@@ -208,37 +212,31 @@ void print_transform(const double R[9], const double t[3]) {
   std::cout << "===============================" << std::endl;
 }
 
-void print_cloud(int64_t n, const icp_las_header& hdr) {
-  std::cout << "  " << n << " points, scale (" << hdr.scale[0] << ", " << hdr.scale[1] << ", " << hdr.scale[2]
-            << "), offset (" << hdr.offset[0] << ", " << hdr.offset[1] << ", " << hdr.offset[2] << ")" << std::endl;
-}
-
 void print_voxel(const Args& a, int64_t ns0, int64_t ns, int64_t nt0, int64_t nt) {
   std::cout << "\nvoxel grid (" << a.voxel << " m)..." << std::endl;
   std::cout << "source: " << ns0 << " -> " << ns << " points\ntarget: " << nt0 << " -> " << nt << " points" << std::endl;
 }
 
-// --voxel, host flow: the cloud replaced by the centroids of its voxels (its own grid, the origin at
-// its minimum).
-bool voxel_reduce(const Args& a, std::vector<double>& xyz) {
-  const int64_t n = (int64_t)xyz.size() / 3;
+// The host flow's reductions: the cloud replaced by what call(in, n, out, &m) keeps of it (m <= n
+// points; false: it failed).
+template <class Call>
+bool replace_cloud(std::vector<double>& xyz, Call call) {
   std::vector<double> out(xyz.size());
-  const int64_t m = icp_voxel_downsample(xyz.data(), n, a.voxel, nullptr, ICP_VOXEL_CENTROID, n, out.data(), nullptr,
-                                         nullptr, nullptr);
-  if (m < 0) return false;
+  int64_t m = 0;
+  if (!call(xyz.data(), (int64_t)xyz.size() / 3, out.data(), &m)) return false;
   out.resize((size_t)m * 3);
   xyz.swap(out);
   return true;
 }
 
-// --voxel, --device-io flow: *d_xyz (n points, a buffer of icp_hip_dev_alloc) replaced by a buffer of
-// the centroids of its voxels; the old buffer is freed.
-bool voxel_reduce_device(const Args& a, icp_hip_ctx* ctx, void** d_xyz, int64_t* n) {
+// The --device-io flow's: *d_xyz (n points, a buffer of icp_hip_dev_alloc) replaced by a buffer of
+// what call(in, n, out, &m) keeps of it; the old buffer is freed.
+template <class Call>
+bool replace_device_cloud(icp_hip_ctx* ctx, void** d_xyz, int64_t* n, Call call) {
   void* d_out = nullptr;
   int64_t m = 0;
   if (icp_hip_dev_alloc(ctx, 3 * sizeof(double) * (size_t)*n, &d_out) != ICP_HIP_OK) return false;
-  if (icp_hip_voxel_downsample_device(ctx, static_cast<double*>(*d_xyz), *n, a.voxel, nullptr, ICP_VOXEL_CENTROID, *n,
-                                      static_cast<double*>(d_out), nullptr, nullptr, &m, nullptr) != ICP_HIP_OK) {
+  if (!call(static_cast<const double*>(*d_xyz), *n, static_cast<double*>(d_out), &m)) {
     (void)icp_hip_dev_free(ctx, d_out);
     return false;
   }
@@ -246,6 +244,21 @@ bool voxel_reduce_device(const Args& a, icp_hip_ctx* ctx, void** d_xyz, int64_t*
   *d_xyz = d_out;
   *n = m;
   return true;
+}
+
+// --voxel: the cloud replaced by the centroids of its voxels (its own grid, the origin at its minimum).
+bool voxel_reduce(const Args& a, std::vector<double>& xyz) {
+  return replace_cloud(xyz, [&](const double* in, int64_t n, double* out, int64_t* m) {
+    *m = icp_voxel_downsample(in, n, a.voxel, nullptr, ICP_VOXEL_CENTROID, n, out, nullptr, nullptr, nullptr);
+    return *m >= 0;
+  });
+}
+
+bool voxel_reduce_device(const Args& a, icp_hip_ctx* ctx, void** d_xyz, int64_t* n) {
+  return replace_device_cloud(ctx, d_xyz, n, [&](const double* in, int64_t n_in, double* out, int64_t* m) {
+    return icp_hip_voxel_downsample_device(ctx, in, n_in, a.voxel, nullptr, ICP_VOXEL_CENTROID, n_in, out, nullptr,
+                                           nullptr, m, nullptr) == ICP_HIP_OK;
+  });
 }
 
 // One outlier filter's line: the points before, the points kept and the threshold.
@@ -274,42 +287,51 @@ std::vector<OutlierPass> outlier_passes(const Args& a) {
   return v;
 }
 
-// --sor / --radius-filter, host flow: the cloud replaced by its kept points, through the device call.
+// --sor / --radius-filter: the cloud replaced by its kept points, through the device call.
 bool outlier_reduce(const Args& a, icp_hip_ctx* ctx, const char* cloud, std::vector<double>& xyz) {
   for (const OutlierPass& f : outlier_passes(a)) {
-    const int64_t n = (int64_t)xyz.size() / 3;
-    std::vector<double> out(xyz.size());
-    int64_t m = 0;
     icp_outlier_stats st{};
-    if (icp_hip_outlier_filter(ctx, xyz.data(), n, f.mode, f.k, f.param, n, out.data(), nullptr, nullptr, &m, &st) !=
-        ICP_HIP_OK)
+    if (!replace_cloud(xyz, [&](const double* in, int64_t n, double* out, int64_t* m) {
+          return icp_hip_outlier_filter(ctx, in, n, f.mode, f.k, f.param, n, out, nullptr, nullptr, m, &st) == ICP_HIP_OK;
+        }))
       return false;
-    out.resize((size_t)m * 3);
-    xyz.swap(out);
     print_outlier(cloud, f.what, st);
   }
   return true;
 }
 
-// --sor / --radius-filter, --device-io flow: *d_xyz (n points, a buffer of icp_hip_dev_alloc) replaced
-// by a buffer of its kept points; the old buffer is freed.
 bool outlier_reduce_device(const Args& a, icp_hip_ctx* ctx, const char* cloud, void** d_xyz, int64_t* n) {
   for (const OutlierPass& f : outlier_passes(a)) {
-    void* d_out = nullptr;
-    int64_t m = 0;
     icp_outlier_stats st{};
-    if (icp_hip_dev_alloc(ctx, 3 * sizeof(double) * (size_t)*n, &d_out) != ICP_HIP_OK) return false;
-    if (icp_hip_outlier_filter_device(ctx, static_cast<double*>(*d_xyz), *n, f.mode, f.k, f.param, *n,
-                                      static_cast<double*>(d_out), nullptr, nullptr, &m, &st) != ICP_HIP_OK) {
-      (void)icp_hip_dev_free(ctx, d_out);
+    if (!replace_device_cloud(ctx, d_xyz, n, [&](const double* in, int64_t n_in, double* out, int64_t* m) {
+          return icp_hip_outlier_filter_device(ctx, in, n_in, f.mode, f.k, f.param, n_in, out, nullptr, nullptr, m, &st) ==
+                 ICP_HIP_OK;
+        }))
       return false;
-    }
-    (void)icp_hip_dev_free(ctx, *d_xyz);
-    *d_xyz = d_out;
-    *n = m;
     print_outlier(cloud, f.what, st);
   }
   return true;
+}
+
+// ICP()'s parameters as the CLI sets them: its flags and rules.
+icp_params cli_params(const Args& a) {
+  icp_params p;
+  icp_params_default(&p);
+  p.max_iterations = a.max_iters;
+  p.tolerance = a.tolerance;
+  p.rules = ICP_RULES_CLI;
+  return p;
+}
+
+// The per-iteration transforms of a run's history, the first cap of them into out; *n_tr counts all.
+void collect_transforms(const icp_result& res, const std::vector<icp_iteration_record>& hist, int32_t cap, double* out,
+                        int32_t* n_tr) {
+  *n_tr = 0;
+  for (int32_t k = 0; k < res.n_history; k++) {
+    if (!hist[k].has_transform) continue;
+    if (*n_tr < cap) std::memcpy(out + 16 * (size_t)*n_tr, hist[k].transform, 16 * sizeof(double));
+    (*n_tr)++;
+  }
 }
 
 // --device-io: the default flow's steps on clouds that stay in HBM (one context; the same files).
@@ -377,11 +399,7 @@ int run_device_io(const Args& a) {
 
   std::cout << "\nparameters: max iterations=" << a.max_iters << ", tolerance=" << a.tolerance << std::endl;
   // ICP() (icp_cli_icp_devices) on the resident clouds: the CLI's octree (10 points, depth 20) and rules
-  icp_params p;
-  icp_params_default(&p);
-  p.max_iterations = a.max_iters;
-  p.tolerance = a.tolerance;
-  p.rules = ICP_RULES_CLI;
+  const icp_params p = cli_params(a);
   const int cap = a.max_iters > 0 ? a.max_iters : 1;
   std::vector<icp_iteration_record> hist((size_t)cap);
   icp_result res;
@@ -398,11 +416,7 @@ int run_device_io(const Args& a) {
   }
   std::vector<double> transforms((size_t)cap * 16);
   int32_t n_tr = 0;
-  for (int32_t k = 0; k < res.n_history; k++) {
-    if (!hist[k].has_transform) continue;
-    if (n_tr < cap) std::memcpy(&transforms[16 * (size_t)n_tr], hist[k].transform, 16 * sizeof(double));
-    n_tr++;
-  }
+  collect_transforms(res, hist, cap, transforms.data(), &n_tr);
   print_transform(res.final_R, res.final_t);
 
   if (icp_hip_write_source_las(ctx, out_path(a, "registered_source.las").c_str(), ICP_LAS_CLI, hs.scale, hs.offset,
@@ -423,11 +437,7 @@ int run_device_io(const Args& a) {
 // the normals estimated once the target is set. src is moved in place.
 int cli_icp_plane(const Args& a, double* src, int64_t ns, const double* tgt, int64_t nt, double R[9], double t[3],
                   double* transforms, int32_t cap, int32_t* n_tr) {
-  icp_params p;
-  icp_params_default(&p);
-  p.max_iterations = a.max_iters;
-  p.tolerance = a.tolerance;
-  p.rules = ICP_RULES_CLI;
+  const icp_params p = cli_params(a);
   std::vector<icp_iteration_record> hist((size_t)cap);
   icp_result res;
   icp_hip_ctx* ctx = nullptr;
@@ -441,13 +451,7 @@ int cli_icp_plane(const Args& a, double* src, int64_t ns, const double* tgt, int
   if (rc != ICP_HIP_OK) return rc;
   std::memcpy(R, res.final_R, sizeof(res.final_R));
   std::memcpy(t, res.final_t, sizeof(res.final_t));
-  int32_t m = 0;
-  for (int32_t k = 0; k < res.n_history; k++) {
-    if (!hist[k].has_transform) continue;
-    if (m < cap) std::memcpy(transforms + 16 * (size_t)m, hist[k].transform, 16 * sizeof(double));
-    m++;
-  }
-  *n_tr = m;
+  collect_transforms(res, hist, cap, transforms, n_tr);
   return ICP_HIP_OK;
 }
 
@@ -519,11 +523,7 @@ int main(int argc, char** argv) {
     return fail(a, "registration failed");
   }
 
-  std::cout << "\n========== transform ==========" << std::endl << "R:" << std::endl;
-  for (int i = 0; i < 3; i++)
-    std::cout << "  [" << R[3 * i] << ", " << R[3 * i + 1] << ", " << R[3 * i + 2] << "]" << std::endl;
-  std::cout << "\nt:\n  [" << t[0] << ", " << t[1] << ", " << t[2] << "]" << std::endl;
-  std::cout << "===============================" << std::endl;
+  print_transform(R, t);
 
   // The source cloud was moved in place by ICP() (:598-605); the target is written unchanged.
   if (icp_las_write_cli(out_path(a, "registered_source.las").c_str(), ss.data(), ns, hs.scale, hs.offset) != 0 ||

@@ -21,6 +21,24 @@ struct GpuOctree {
   int32_t max_depth = -1, max_inner_depth = -1, pos_of_orig0 = 0;
 };
 
+// The owner of a built tree's two device arrays: freed at the scope's end unless released.
+struct ScopedOctree {
+  GpuOctree t;
+  ScopedOctree() = default;
+  ScopedOctree(const ScopedOctree&) = delete;
+  ScopedOctree& operator=(const ScopedOctree&) = delete;
+  ~ScopedOctree() {
+    if (t.nodes) (void)hipFree(t.nodes);
+    if (t.pts) (void)hipFree(t.pts);
+  }
+  // The tree leaves the owner (its arrays outlive the scope) and is returned.
+  GpuOctree release() {
+    const GpuOctree r = t;
+    t = GpuOctree();
+    return r;
+  }
+};
+
 // xyz: device AoS target (n points). Runs on stream s and synchronizes it before returning.
 // Returns 0 on success, 1 on invalid input (non-finite coordinates, n out of range, max_d > 21),
 // -2 out of device memory, -3 other device errors; *why says what.

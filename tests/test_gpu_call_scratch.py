@@ -1,7 +1,9 @@
 """The calls that own device memory for their own length (csrc/dev_scratch.h), repeated on one
 context: set_target, set_source, an iterate, get_source, get_correspondences, nn / nn_device with
 each output null in turn, knn / knn_device with k = 1 and 16, estimate_target_normals,
-set_target_normals / get_target_normals in host and device forms, and plane_sums.
+set_target_normals / get_target_normals in host and device forms, plane_sums, and the cloud filters
+voxel_downsample and outlier_filter (statistical with k = 1 and min(16, n - 1), radius) with their
+_device forms, each output null in turn and all null.
 
 A second pass of the sequence on a context that has already run it must return the bytes of the
 first pass, and both the bytes of a fresh context: a scratch buffer released before the work that
@@ -42,6 +44,76 @@ def _p(a):
 
 def _d(b):
     return None if b is None else C.c_void_p(b.ptr)
+
+
+def _kept_untouched(m, cap_arrays, want):
+    """Past m, and wherever it was not asked for, an output still holds its sentinel."""
+    for a, w in zip(cap_arrays, want):
+        rest = a[m if w else 0:]
+        assert np.isnan(rest).all() if a.dtype.kind == "f" else (rest == -7).all()
+
+
+def _filters(icp, ctx, q, n, out):
+    """The voxel grid and the outlier filters on q, host and device forms, every choice of outputs."""
+    L, h = icp.lib(), ctx.handle
+    choices = ((1, 1, 1), (0, 1, 1), (1, 0, 1), (1, 1, 0), (0, 0, 0))
+    sent = (np.full((n, 3), np.nan), np.full(n, -7, np.int32), np.full(n, -7, np.int32), np.full(n, np.nan))
+    modes = (("sor 1", icp.OUTLIER_STATISTICAL, 1, 1.0), (f"sor {min(16, n - 1)}", icp.OUTLIER_STATISTICAL, min(16, n - 1), 1.0),
+             ("radius", icp.OUTLIER_RADIUS, 1, 5.0))
+    with ctx.to_device(q) as d_q, ctx.device_buffer(24 * n) as d_p, ctx.device_buffer(4 * n) as d_a, \
+            ctx.device_buffer(4 * n) as d_b, ctx.device_buffer(8 * n) as d_s:
+        def fill():
+            for buf, a in zip((d_p, d_a, d_b, d_s), sent):
+                buf.upload(a)
+            return [a.copy() for a in sent]
+
+        def down():
+            return [d_p.download(np.float64, (n, 3)), d_a.download(np.int32, (n,)), d_b.download(np.int32, (n,)),
+                    d_s.download(np.float64, (n,))]
+
+        for want in choices:
+            name = "voxel " + "".join(map(str, want))
+            p, f, k, _ = fill()
+            m, org = C.c_int64(-1), np.full(3, np.nan)
+            assert L.icp_hip_voxel_downsample(h, _p(q), n, 5.0, None, icp.VOXEL_CENTROID, n, _p(p) if want[0] else None,
+                                              _p(f) if want[1] else None, _p(k) if want[2] else None, C.byref(m),
+                                              _p(org)) == 0
+            assert 1 <= m.value <= n
+            _kept_untouched(m.value, (p, f, k), want)
+            out[name] = bytes(m) + org.tobytes() + p.tobytes() + f.tobytes() + k.tobytes()
+            m, org = C.c_int64(-1), np.full(3, np.nan)
+            assert L.icp_hip_voxel_downsample_device(h, _d(d_q), n, 5.0, None, icp.VOXEL_CENTROID, n,
+                                                     _d(d_p) if want[0] else None, _d(d_a) if want[1] else None,
+                                                     _d(d_b) if want[2] else None, C.byref(m), _p(org)) == 0
+            p, f, k, _ = down()
+            out[name + " device"] = bytes(m) + org.tobytes() + p.tobytes() + f.tobytes() + k.tobytes()
+            assert out[name + " device"] == out[name]
+        for label, mode, k, param in modes if n >= 2 else ():
+            for want in choices:
+                name = f"outlier {label} " + "".join(map(str, want))
+                p, ix, _, sc = fill()
+                m, st = C.c_int64(-1), icp.OutlierStats()
+                assert L.icp_hip_outlier_filter(h, _p(q), n, mode, k, param, n, _p(p) if want[0] else None,
+                                                _p(ix) if want[1] else None, _p(sc) if want[2] else None, C.byref(m),
+                                                C.byref(st)) == 0
+                assert 0 <= m.value <= n and st.n == n and st.kept == m.value
+                _kept_untouched(m.value, (p, ix), want)
+                assert np.isnan(sc).all() if not want[2] else not np.isnan(sc).any()
+                out[name] = bytes(m) + bytes(st) + p.tobytes() + ix.tobytes() + sc.tobytes()
+                m, st = C.c_int64(-1), icp.OutlierStats()
+                assert L.icp_hip_outlier_filter_device(h, _d(d_q), n, mode, k, param, n, _d(d_p) if want[0] else None,
+                                                       _d(d_a) if want[1] else None, _d(d_s) if want[2] else None,
+                                                       C.byref(m), C.byref(st)) == 0
+                p, ix, _, sc = down()
+                out[name + " device"] = bytes(m) + bytes(st) + p.tobytes() + ix.tobytes() + sc.tobytes()
+                assert out[name + " device"] == out[name]
+        if n < 2:  # a usage error by the interface, in both forms; m is reported as 0
+            for call, cloud, outs in ((L.icp_hip_outlier_filter, _p(q), (_p(sent[0].copy()), None, None)),
+                                      (L.icp_hip_outlier_filter_device, _d(d_q), (_d(d_p), None, None))):
+                m = C.c_int64(-1)
+                assert call(h, cloud, n, icp.OUTLIER_STATISTICAL, 1, 1.0, n, *outs, C.byref(m), None) == icp.EINVAL
+                assert m.value == 0
+        assert d_q.download(np.float64).tobytes() == q.tobytes()  # inputs are never written
 
 
 def _sequence(icp, ctx, n, group):
@@ -107,6 +179,7 @@ def _sequence(icp, ctx, n, group):
         assert e.value.code == icp.EINVAL
     elif "stats" in out:
         out["plane_sums"] = bytes(memoryview(ctx.plane_sums(src.mean(0))))
+    _filters(icp, ctx, q, n, out)
     return out
 
 
@@ -127,9 +200,11 @@ def _check_passes(icp, make, n, group):
 def test_repeated_calls_return_the_same_bytes(icp, n):
     out = _check_passes(icp, lambda: icp.Context(0), n, False)
     assert "plane_sums" in out and "knn_device 16" in out
+    assert "voxel 000 device" in out and ("outlier radius 110 device" in out) == (n >= 2)
 
 
 @pytest.mark.parametrize("n", SIZES)
 def test_repeated_calls_on_a_group_of_two(icp, n):
     out = _check_passes(icp, lambda: icp.Context(devices=[0, 0], transport=icp.XPORT_HOST), n, True)
     assert ("stats" in out) == (n >= 2) and "knn_device 16" in out
+    assert "voxel 000 device" in out and ("outlier radius 110 device" in out) == (n >= 2)
