@@ -139,6 +139,41 @@ int icp_session_last_plane(const icp_session* s, icp_plane_sums* out, int32_t* u
 /* icp_engine_run with a metric. */
 int icp_engine_run_metric(icp_hip_ctx* ctx, const icp_params* p, int32_t metric, icp_result* res,
                           icp_iteration_record* history, int32_t history_cap, const icp_engine_hooks* hooks);
+/* The correspondence rejector of a session's steps. ICP_REJECT_SIGMA (the default) is the
+ * reference's cull, d <= mean + k std: the session is then exactly what it is without this call.
+ * With ICP_REJECT_TRIM (param = the fraction of the finite pairs kept, in (0, 1]) or
+ * ICP_REJECT_MAX_DIST (param = the largest residual of a valid pair, > 0 and finite) a step
+ *   1. runs icp_hip_iterate as every session does (and pays for its cull),
+ *   2. takes its threshold t from icp_hip_residual_select(fraction, 0) (TRIM; 0 when no residual is
+ *      finite) or from param (MAX_DIST),
+ *   3. takes icp_hip_pair_sums(t), and
+ *   4. takes the loop's decisions (convergence, divergence, too few) and the best fit from that
+ *      call's rmse, valid, centroids and H in place of the cull's, by the same code.
+ * With ICP_METRIC_PLANE a step that fits takes icp_hip_plane_sums_at(origin = the pair sums'
+ * centroid_src, t), then icp_plane_solve, and the SVD increment when the solve refuses. The record of
+ * the iteration carries t as threshold, the rejector's valid_points, outlier_points and rmse, and the
+ * iterate's own mean and std. Such a session steps on the host (never the device-resident loop).
+ * Call it before the first step: later it returns ICP_HIP_EINVAL, as it does for another mode, a
+ * param outside the mode's range, and for TRIM or MAX_DIST on a multi-device context or one with a
+ * communicator. */
+#define ICP_REJECT_SIGMA    0   /* the reference's cull: the default */
+#define ICP_REJECT_TRIM     1   /* param = fraction kept, (0, 1] */
+#define ICP_REJECT_MAX_DIST 2   /* param = largest residual of a valid pair, > 0, finite */
+int icp_session_set_rejection(icp_session* s, int32_t mode, double param);
+/* icp_engine_run with its options in a versioned record, so that the next option needs no entry
+ * point of its own: set version = ICP_RUN_OPTIONS_VERSION (icp_run_options_default does); another
+ * version is ICP_HIP_EINVAL. metric as icp_session_set_metric, reject and reject_param as
+ * icp_session_set_rejection. The defaults give icp_engine_run. */
+#define ICP_RUN_OPTIONS_VERSION 1u
+typedef struct icp_run_options {
+  uint32_t version;
+  int32_t metric;       /* ICP_METRIC_* */
+  int32_t reject;       /* ICP_REJECT_* */
+  double reject_param;
+} icp_run_options;
+void icp_run_options_default(icp_run_options* opt);
+int icp_engine_run_options(icp_hip_ctx* ctx, const icp_params* p, const icp_run_options* opt, icp_result* res,
+                           icp_iteration_record* history, int32_t history_cap, const icp_engine_hooks* hooks);
 int icp_session_finish(icp_session* s, icp_result* res);
 /* Current cumulative transform (row-major 4x4). */
 void icp_session_transform(const icp_session* s, double T_cum[16]);

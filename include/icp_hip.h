@@ -508,6 +508,54 @@ int icp_hip_plane_sums(icp_hip_ctx* ctx, const double origin[3], icp_plane_sums*
  * entry of A is not positive, or a pivot of the scaled matrix is at most 2^-26. */
 void icp_plane_solve(const icp_plane_sums* sums, double T[16], int32_t* ok);
 
+/* --- Correspondence rejectors beside the reference's cull: a rank select over
+ * the last iterate's residuals and the valid-pair sums at a caller's threshold. Calls of their own
+ * after icp_hip_iterate: they read what it left resident and write none of it. All three are
+ * ICP_HIP_ENOTREADY without a target or before an iterate on this source, and ICP_HIP_EINVAL on a
+ * multi-device context and on one with a communicator (the residuals and the sums are not exchanged
+ * between ranks), each before any kernel runs. */
+typedef struct icp_select_result {
+  double  value;     /* the rank-th smallest finite residual (1-based) */
+  int64_t rank;      /* the rank used */
+  int64_t n_finite;  /* finite residuals of the source */
+  int64_t n_less;    /* finite residuals <  value */
+  int64_t n_equal;   /* finite residuals == value (>= 1) */
+} icp_select_result;
+
+/* The rank-th smallest finite residual of the last iterate, exactly. A finite residual is sqrt of a
+ * non-negative fp64, so its bit pattern orders as an unsigned 64-bit integer: that is the key; NaN
+ * and +-inf are not ranked, they are counted out of n_finite. rank >= 1 selects that rank (fraction
+ * is ignored); rank == 0 selects icp_trim_rank(fraction, n_finite) (icp_host.h), fraction in (0, 1],
+ * computed on the device once n_finite is known. Deterministic: the value and the three counts
+ * depend on the multiset of residuals only. A radix select, most significant digit first, of six
+ * passes chained on the stream: one host wait per call.
+ * ICP_HIP_EINVAL: rank < 0; rank == 0 with a fraction outside (0, 1] or NaN; a null argument (all
+ * before any kernel runs); no finite residual; rank > n_finite (out->n_finite is then filled, the
+ * other fields are zero). */
+int icp_hip_residual_select(icp_hip_ctx* ctx, double fraction, int64_t rank, icp_select_result* out);
+
+typedef struct icp_pair_sums {
+  double  threshold;
+  int64_t n_finite;
+  int64_t valid;            /* finite d with d <= threshold */
+  double  sum_d2, rmse;     /* sum of d*d over the valid pairs; sqrt(sum_d2 / valid), 0 when valid == 0 */
+  double  centroid_src[3], centroid_tgt[3];
+  double  H[9];             /* sum (a - ca)(b - cb)^T, row-major, as icp_iter_stats */
+} icp_pair_sums;
+
+/* The statistics icp_iter_stats carries of the cull's valid pairs, of the pairs with a finite
+ * d <= threshold instead. threshold may be +inf (every finite pair); NaN is ICP_HIP_EINVAL. The sums
+ * are centred as the iterate's: plain sums of values shifted by the first valid pair, over fixed
+ * parts of 4096 queries, a fixed tree inside a part, the parts added in index order, then (count,
+ * means, co-moment): the bytes depend neither on the run nor on which search path settled which
+ * query. With valid == 0 the centroids and H are zeros. One host wait per call. */
+int icp_hip_pair_sums(icp_hip_ctx* ctx, double threshold, icp_pair_sums* out);
+
+/* icp_hip_plane_sums over the pairs with a finite d <= threshold in place of the iterate's own
+ * threshold (which gives icp_hip_plane_sums' bytes). Also ICP_HIP_ENOTREADY without normals and
+ * ICP_HIP_EINVAL for a NaN threshold or a non-finite origin. */
+int icp_hip_plane_sums_at(icp_hip_ctx* ctx, const double origin[3], double threshold, icp_plane_sums* out);
+
 /* --- Voxel-grid down-sampling. Beside everything above: it needs no target and no
  * source and touches neither.
  * n points (AoS xyz, fp64), a voxel edge `voxel` and an origin o: the caller's, or with null the

@@ -44,6 +44,12 @@ void icp_cov_from_pairs(const double* a_xyz, const double* b_xyz, const double* 
                         double out20[20]);
 void icp_cov_merge(const double* parts20, int32_t nparts, double out20[20]);
 double icp_cull_threshold(double mean, double sd, double k_sigma, int iter, int engine_rules);
+/* The trimmed rejector's rank (icp_hip_residual_select with rank 0): of n_finite ranked residuals
+ * the fraction kept, at least 3 (all of fewer):
+ *   max(min(3, n_finite), min(n_finite, (int64_t)(fraction * (double)n_finite)))
+ * with the product evaluated in fp64 as written (one multiplication, one truncation: the device
+ * computes the same bits). 0 for a fraction outside (0, 1] or NaN, or a negative n_finite. */
+int64_t icp_trim_rank(double fraction, int64_t n_finite);
 
 /* Spatial sharding of the source for the multi-GPU path: order[] = a permutation of 0..n-1 in
  * which every contiguous range is spatially compact (kd buckets, the query order of the search

@@ -28,6 +28,8 @@ OK, EINVAL, ENOMEM, EDEVICE, ERCCL, ENOTREADY, EEXCHANGE = 0, -1, -2, -3, -4, -5
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2  # icp_hip_dev_copy directions
 DBG_SLOTS = 40
 METRIC_POINT, METRIC_PLANE = 0, 1  # icp_engine.h ICP_METRIC_*
+REJECT_SIGMA, REJECT_TRIM, REJECT_MAX_DIST = 0, 1, 2  # icp_engine.h ICP_REJECT_*
+RUN_OPTIONS_VERSION = 1  # icp_engine.h ICP_RUN_OPTIONS_VERSION
 KNN_MAX = 32
 VOXEL_CENTROID, VOXEL_FIRST = 0, 1  # icp_hip.h ICP_VOXEL_*
 OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1  # icp_hip.h ICP_OUTLIER_*
@@ -162,6 +164,24 @@ class PlaneSums(C.Structure):
     ]
 
 
+class SelectResult(C.Structure):
+    """icp_select_result (include/icp_hip.h): a rank select over the last iterate's residuals."""
+    _fields_ = [("value", C.c_double), ("rank", C.c_int64), ("n_finite", C.c_int64), ("n_less", C.c_int64),
+                ("n_equal", C.c_int64)]
+
+
+class PairSums(C.Structure):
+    """icp_pair_sums (include/icp_hip.h): the valid-pair statistics at a caller's threshold."""
+    _fields_ = [("threshold", C.c_double), ("n_finite", C.c_int64), ("valid", C.c_int64), ("sum_d2", C.c_double),
+                ("rmse", C.c_double), ("centroid_src", C.c_double * 3), ("centroid_tgt", C.c_double * 3),
+                ("H", C.c_double * 9)]
+
+
+class RunOptions(C.Structure):
+    """icp_run_options (include/icp_engine.h): the options of icp_engine_run_options."""
+    _fields_ = [("version", C.c_uint32), ("metric", C.c_int32), ("reject", C.c_int32), ("reject_param", C.c_double)]
+
+
 class OutlierStats(C.Structure):
     """icp_outlier_stats (include/icp_hip.h): what an outlier call reports beside its arrays."""
     _fields_ = [("n", C.c_int64), ("kept", C.c_int64), ("mean", C.c_double), ("std", C.c_double),
@@ -208,6 +228,9 @@ SIGNATURES = {
     "icp_hip_get_target_normals_device": (C.c_int, [_P, _P]),
     "icp_hip_plane_sums": (C.c_int, [_P, _P, C.POINTER(PlaneSums)]),
     "icp_plane_solve": (None, [C.POINTER(PlaneSums), _P, _I32]),
+    "icp_hip_residual_select": (C.c_int, [_P, C.c_double, C.c_int64, C.POINTER(SelectResult)]),
+    "icp_hip_pair_sums": (C.c_int, [_P, C.c_double, C.POINTER(PairSums)]),
+    "icp_hip_plane_sums_at": (C.c_int, [_P, _P, C.c_double, C.POINTER(PlaneSums)]),
     "icp_hip_voxel_downsample": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, C.c_int, C.c_int64, _P, _P, _P,
                                            C.POINTER(C.c_int64), _P]),
     "icp_hip_voxel_downsample_device": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, C.c_int, C.c_int64, _P, _P, _P,
@@ -254,6 +277,10 @@ SIGNATURES = {
     "icp_session_last_plane": (C.c_int, [_P, C.POINTER(PlaneSums), _I32]),
     "icp_engine_run_metric": (C.c_int, [_P, C.POINTER(Params), C.c_int32, C.POINTER(Result),
                                         C.POINTER(IterationRecord), C.c_int32, C.POINTER(Hooks)]),
+    "icp_session_set_rejection": (C.c_int, [_P, C.c_int32, C.c_double]),
+    "icp_run_options_default": (None, [C.POINTER(RunOptions)]),
+    "icp_engine_run_options": (C.c_int, [_P, C.POINTER(Params), C.POINTER(RunOptions), C.POINTER(Result),
+                                         C.POINTER(IterationRecord), C.c_int32, C.POINTER(Hooks)]),
     "icp_session_transform": (None, [_P, _P]),
     "icp_session_destroy": (None, [_P]),
     "icp_cli_icp": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_double, _P, _P, _P, C.c_int32,
@@ -275,6 +302,7 @@ SIGNATURES = {
     "icp_cov_from_pairs": (None, [_P, _P, _P, C.c_int64, C.c_double, _P]),
     "icp_cov_merge": (None, [_P, C.c_int32, _P]),
     "icp_cull_threshold": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_int, C.c_int]),
+    "icp_trim_rank": (C.c_int64, [C.c_double, C.c_int64]),
     "icp_synth_default": (None, [C.POINTER(SynthSpec)]),
     "icp_synth_pair": (C.c_int, [C.POINTER(SynthSpec), C.c_int64, C.c_int64, _P, _P, _P]),
     "icp_source_shard_order": (C.c_int, [_P, C.c_int64, _P]),
@@ -557,6 +585,31 @@ class Context:
         _check(lib().icp_hip_plane_sums(self._h, _ptr(o), C.byref(out)))
         return out
 
+    # --- the rejectors (include/icp_hip.h): rank select, pair sums and plane sums at a threshold
+    def residual_select(self, fraction: float = 1.0, rank: int = 0) -> SelectResult:
+        """The rank-th smallest finite residual of the last iterate (rank 0: trim_rank(fraction,
+        n_finite)). An IcpError of a rank past n_finite carries n_finite in its attribute n_finite."""
+        out = SelectResult()
+        rc = lib().icp_hip_residual_select(self._h, fraction, rank, C.byref(out))
+        if rc != 0:
+            e = IcpError(rc, lib().icp_hip_last_error().decode(errors="replace"))
+            e.n_finite = out.n_finite
+            raise e
+        return out
+
+    def pair_sums(self, threshold: float) -> PairSums:
+        """The valid-pair statistics of the last iterate over the pairs with a finite d <= threshold."""
+        out = PairSums()
+        _check(lib().icp_hip_pair_sums(self._h, threshold, C.byref(out)))
+        return out
+
+    def plane_sums_at(self, origin, threshold: float) -> PlaneSums:
+        """plane_sums over the pairs with a finite d <= threshold."""
+        o = np.ascontiguousarray(origin, np.float64).reshape(3)
+        out = PlaneSums()
+        _check(lib().icp_hip_plane_sums_at(self._h, _ptr(o), threshold, C.byref(out)))
+        return out
+
     # --- voxel-grid down-sampling (include/icp_hip.h; the host's: voxel_downsample below)
     def voxel_downsample(self, xyz, voxel, origin=None, mode=VOXEL_CENTROID, cap=None, count_only=False):
         """The voxels of an (n, 3) cloud: (xyz (m, 3), first (m,), count (m,), origin (3,)), or with
@@ -782,18 +835,38 @@ class Context:
         _check(lib().icp_hip_debug_counters(self._h, _ptr(out)))
         return {name: int(out[k]) for k, name in DBG_NAMES.items()}
 
-    def session(self, params: Params, metric: int | None = None) -> "Session":
-        """metric None: the session's default (ICP_METRIC_POINT), no icp_session_set_metric call."""
-        return Session(self, params, metric=metric)
+    def session(self, params: Params, metric: int | None = None, reject=None) -> "Session":
+        """metric None: the session's default (ICP_METRIC_POINT), no icp_session_set_metric call.
+        reject = (mode, param): icp_session_set_rejection; None: no such call (ICP_REJECT_SIGMA)."""
+        return Session(self, params, metric=metric, reject=reject)
 
-    def run(self, params: Params, history_cap: int = 1024, metric: int = METRIC_POINT):
+    def run(self, params: Params, history_cap: int = 1024, metric: int = METRIC_POINT, reject=None):
+        """reject = (mode, param): the run goes through icp_engine_run_options."""
         res = Result()
         hist = (IterationRecord * max(1, history_cap))()
-        if metric == METRIC_POINT:
+        if reject is not None:
+            opt = run_options(metric=metric, reject=reject[0], reject_param=reject[1])
+            rc = lib().icp_engine_run_options(self._h, C.byref(params), C.byref(opt), C.byref(res), hist, history_cap,
+                                              None)
+        elif metric == METRIC_POINT:
             rc = lib().icp_engine_run(self._h, C.byref(params), C.byref(res), hist, history_cap, None)
         else:
             rc = lib().icp_engine_run_metric(self._h, C.byref(params), metric, C.byref(res), hist, history_cap, None)
         return rc, res, [hist[k] for k in range(res.n_history)]
+
+
+def run_options(**kw) -> RunOptions:
+    """icp_run_options with the library defaults, then the given fields."""
+    o = RunOptions()
+    lib().icp_run_options_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def trim_rank(fraction: float, n_finite: int) -> int:
+    """icp_trim_rank (host, no GPU): the trimmed rejector's rank."""
+    return int(lib().icp_trim_rank(fraction, n_finite))
 
 
 def _origin3(origin):
@@ -894,13 +967,20 @@ class DeviceBuffer:
 class Session:
     """Steppable ICP loop on a context (icp_session_*): one step = one reference loop body."""
 
-    def __init__(self, ctx: Context, params: Params, metric: int | None = None):
+    def __init__(self, ctx: Context, params: Params, metric: int | None = None, reject=None):
         self._ctx = ctx  # keep alive
         self._h = C.c_void_p()
         _check(lib().icp_session_create(ctx.handle, C.byref(params), None, C.byref(self._h)))
         self.done = False
         if metric is not None:
             self.set_metric(metric)
+        if reject is not None:
+            self.set_rejection(*reject)
+
+    def set_rejection(self, mode: int, param: float = 0.0):
+        """ICP_REJECT_SIGMA / _TRIM (fraction kept) / _MAX_DIST (metres), before the first step
+        (icp_session_set_rejection)."""
+        _check(lib().icp_session_set_rejection(self._h, mode, param))
 
     def set_metric(self, metric: int):
         """ICP_METRIC_POINT / ICP_METRIC_PLANE, before the first step (icp_session_set_metric)."""
@@ -966,12 +1046,29 @@ class Session:
 
 
 def engine_register(params: Params, src, tgt, device: int = -1, history_cap: int = 1024, stop_flag=None,
-                    on_log=None, on_progress=None, stop_at: int = -1, devices=None):
+                    on_log=None, on_progress=None, stop_at: int = -1, devices=None, metric: int = METRIC_POINT,
+                    reject=None, normals_k: int = 16):
     """ICPEngine::registerPointClouds drop-in. Returns (rc, result, history, src_out).
     stop_at >= 0 raises the stop flag from the progress hook of that iteration (the reference's
-    cross-thread ICPEngine::stop(), checked at the next iteration, icpengine.cpp:160)."""
+    cross-thread ICPEngine::stop(), checked at the next iteration, icpengine.cpp:160).
+    metric / reject = (mode, param): the registration's steps on one context through
+    icp_engine_run_options (one device, no hooks; the plane metric's normals from normals_k
+    neighbours); the source is written back when the run finished, as the engine does."""
     src = _aos(src).copy()
     tgt = _aos(tgt)
+    if metric != METRIC_POINT or reject is not None:
+        cli = params.rules == RULES_CLI
+        with Context(device if devices is None else devices[0]) as ctx:
+            ctx.set_target(tgt, 10 if cli else params.octree_max_points, 20 if cli else params.octree_max_depth,
+                           params.rules)
+            if metric == METRIC_PLANE:
+                ctx.estimate_target_normals(normals_k)
+            ctx.set_source(src)
+            rc, res, hist = ctx.run(params, history_cap, metric=metric,
+                                    reject=reject if reject is not None else (REJECT_SIGMA, 0.0))
+            if rc == 0:
+                src = ctx.get_source()
+        return rc, res, hist, src
     res = Result()
     hist = (IterationRecord * max(1, history_cap))()
     hooks = None

@@ -189,12 +189,14 @@ int icp_hip_get_target_normals_device(icp_hip_ctx* c, double* d_n_xyz_out) {
   return ICP_HIP_OK;
 }
 
-int icp_hip_plane_sums(icp_hip_ctx* c, const double origin[3], icp_plane_sums* out) {
+// icp_hip_plane_sums (thr null: the device record's threshold) and icp_hip_plane_sums_at.
+static int plane_sums_core(icp_hip_ctx* c, const double origin[3], const double* thr, icp_plane_sums* out) {
   if (!c || !origin || !out) return fail(ICP_HIP_EINVAL, "null argument");
   if (c->group) return fail(ICP_HIP_EINVAL, "plane_sums: not on a multi-device context (the sums are not exchanged)");
   if (c->comm || c->xfn) return fail(ICP_HIP_EINVAL, "plane_sums: not on a context with a communicator (the sums are not exchanged)");
   for (int a = 0; a < 3; a++)
     if (!(origin[a] - origin[a] == 0.0)) return fail(ICP_HIP_EINVAL, "plane_sums: non-finite origin");
+  if (thr && *thr != *thr) return fail(ICP_HIP_EINVAL, "plane_sums_at: the threshold is NaN");
   if (!c->nodes) return fail(ICP_HIP_ENOTREADY, "target not set");
   if (!c->normals) return fail(ICP_HIP_ENOTREADY, "the target has no normals");
   if (!c->have_results) return fail(ICP_HIP_ENOTREADY, "no iteration has run on this source");
@@ -219,8 +221,9 @@ int icp_hip_plane_sums(icp_hip_ctx* c, const double origin[3], icp_plane_sums* o
   a.n = c->n_src;
   a.parts = c->plane_parts;
   a.out = c->plane_parts + (size_t)c->plane_cap * kPlaneSums;
+  a.thr = thr ? *thr : 0.0;
   double h[kPlaneSums];
-  HIP_TRY(launch_plane_sums(a, c->stream));
+  HIP_TRY(thr ? launch_plane_sums_at(a, c->stream) : launch_plane_sums(a, c->stream));
   HIP_TRY(hipMemcpyAsync(h, a.out, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the call's one host wait
   std::memset(out, 0, sizeof(*out));
@@ -237,6 +240,14 @@ int icp_hip_plane_sums(icp_hip_ctx* c, const double origin[3], icp_plane_sums* o
   out->n_skipped = (int64_t)h[29];
   for (int k = 0; k < 3; k++) out->origin[k] = origin[k];
   return ICP_HIP_OK;
+}
+
+int icp_hip_plane_sums(icp_hip_ctx* c, const double origin[3], icp_plane_sums* out) {
+  return plane_sums_core(c, origin, nullptr, out);
+}
+
+int icp_hip_plane_sums_at(icp_hip_ctx* c, const double origin[3], double threshold, icp_plane_sums* out) {
+  return plane_sums_core(c, origin, &threshold, out);
 }
 
 void icp_plane_solve(const icp_plane_sums* sums, double T[16], int32_t* ok) { icp::plane_solve(sums, T, ok); }

@@ -103,6 +103,8 @@ struct icp_session {
   int32_t metric = ICP_METRIC_POINT;
   icp_plane_sums plane{};  // the last step's sums (plane metric)
   int32_t used_plane = 0;  // the last step's increment came from the plane solve
+  int32_t reject = ICP_REJECT_SIGMA;
+  double reject_param = 0.0;  // TRIM: the fraction kept; MAX_DIST: the largest residual of a valid pair
 };
 
 extern "C" {
@@ -138,6 +140,24 @@ int icp_session_set_metric(icp_session* s, int32_t metric) {
     if (!c->normals) return fail(ICP_HIP_ENOTREADY, "set_metric: the target has no normals");
   }
   s->metric = metric;
+  return ICP_HIP_OK;
+}
+
+int icp_session_set_rejection(icp_session* s, int32_t mode, double param) {
+  if (!s || (mode != ICP_REJECT_SIGMA && mode != ICP_REJECT_TRIM && mode != ICP_REJECT_MAX_DIST))
+    return fail(ICP_HIP_EINVAL, "set_rejection: bad arguments");
+  if (mode == ICP_REJECT_TRIM && !(param > 0.0 && param <= 1.0))
+    return fail(ICP_HIP_EINVAL, "set_rejection: the fraction kept is not in (0, 1]");
+  if (mode == ICP_REJECT_MAX_DIST && !(param > 0.0 && param - param == 0.0))
+    return fail(ICP_HIP_EINVAL, "set_rejection: the maximum distance is not positive and finite");
+  if (s->core.iter != 0) return fail(ICP_HIP_EINVAL, "set_rejection: the session has already stepped");
+  if (mode != ICP_REJECT_SIGMA) {
+    const icp_hip_ctx* c = s->ctx;
+    if (c->group) return fail(ICP_HIP_EINVAL, "set_rejection: the rejectors do not run on a multi-device context");
+    if (c->comm || c->xfn) return fail(ICP_HIP_EINVAL, "set_rejection: the rejectors do not run with a communicator");
+  }
+  s->reject = mode;
+  s->reject_param = mode == ICP_REJECT_SIGMA ? 0.0 : param;
   return ICP_HIP_OK;
 }
 
@@ -235,16 +255,45 @@ int icp_session_step(icp_session* s, icp_iteration_record* rec, int32_t* produce
     const double k_sigma = cli ? 3.0 : p.sigma_multiplier;  // CLI hard-codes 3.0 (:523)
     const int iter = s->core.iter;
     icp_iter_stats st;
-    const int rc = icp_hip_iterate(s->ctx, s->core.pending ? s->core.T : nullptr, iter, p.rules, k_sigma, &st);
-    if (rc != ICP_HIP_OK) {
-      s->rc_final = rc;
+    // a device call of the step failed: the session ends with its code and message
+    auto failed = [&](int code, bool count_iteration) {
+      s->rc_final = code;
       std::snprintf(s->message, sizeof(s->message), "%s", icp_hip_last_error());
-      s->core.iter++;
+      if (count_iteration) s->core.iter++;
       s->core.done = 1;
       if (done) *done = 1;
-      return rc;
-    }
+      return code;
+    };
+    const int rc = icp_hip_iterate(s->ctx, s->core.pending ? s->core.T : nullptr, iter, p.rules, k_sigma, &st);
+    if (rc != ICP_HIP_OK) return failed(rc, true);
     s->core.pending = 0;
+    const bool rejector = s->reject != ICP_REJECT_SIGMA;
+    double tau = st.threshold;
+    if (rejector) {
+      // the rejector's threshold and the statistics of its valid pairs in place of the cull's: the
+      // decisions below are the same code on them. The record keeps the iterate's own mean, std,
+      // min_d, max_d and n_bad. Without a finite residual nothing is ranked: no pair is valid.
+      tau = s->reject_param;
+      if (s->reject == ICP_REJECT_TRIM) {
+        tau = 0.0;
+        if (st.n - st.n_bad > 0) {
+          icp_select_result sel;
+          const int src = icp_hip_residual_select(s->ctx, s->reject_param, 0, &sel);
+          if (src != ICP_HIP_OK) return failed(src, true);
+          tau = sel.value;
+        }
+      }
+      icp_pair_sums ps;
+      const int prc = icp_hip_pair_sums(s->ctx, tau, &ps);
+      if (prc != ICP_HIP_OK) return failed(prc, true);
+      st.threshold = tau;
+      st.valid = ps.valid;
+      st.rmse = ps.rmse;
+      st.sum_d2 = ps.sum_d2;
+      std::memcpy(st.centroid_src, ps.centroid_src, sizeof(st.centroid_src));
+      std::memcpy(st.centroid_tgt, ps.centroid_tgt, sizeof(st.centroid_tgt));
+      std::memcpy(st.H, ps.H, sizeof(st.H));
+    }
     double Tc_before[16];
     std::memcpy(Tc_before, s->core.Tc, sizeof(Tc_before));
     const int32_t outcome = icp::session_core_step(s->core, s->sp, st.rmse, st.valid, st.centroid_src,
@@ -255,14 +304,9 @@ int icp_session_step(icp_session* s, icp_iteration_record* rec, int32_t* produce
       std::memset(&s->plane, 0, sizeof(s->plane));
       s->used_plane = 0;
       if (outcome == icp::kStepTransform) {
-        const int prc = icp_hip_plane_sums(s->ctx, st.centroid_src, &s->plane);
-        if (prc != ICP_HIP_OK) {
-          s->rc_final = prc;
-          std::snprintf(s->message, sizeof(s->message), "%s", icp_hip_last_error());
-          s->core.done = 1;
-          if (done) *done = 1;
-          return prc;
-        }
+        const int prc = rejector ? icp_hip_plane_sums_at(s->ctx, st.centroid_src, tau, &s->plane)
+                                 : icp_hip_plane_sums(s->ctx, st.centroid_src, &s->plane);
+        if (prc != ICP_HIP_OK) return failed(prc, false);
         double Tp[16];
         icp_plane_solve(&s->plane, Tp, &s->used_plane);
         if (s->used_plane) {
@@ -291,8 +335,10 @@ static int session_run(icp_session* s, int32_t k, int32_t* steps_done, int32_t* 
   // (icpengine.cpp:160-164; a flag raised from a progress hook stops the next iteration): such a
   // session steps on the host.
   const bool per_iteration_stop = s->h && s->h->stop_flag;
-  // a plane session steps on the host too (its increment is not the device step's)
-  if (icp_hip_loop_eligible(s->ctx) && !per_iteration_stop && s->metric == ICP_METRIC_POINT) {
+  // a plane session steps on the host too (its increment is not the device step's), and so does
+  // one with a rejector (its statistics are not the device record's)
+  if (icp_hip_loop_eligible(s->ctx) && !per_iteration_stop && s->metric == ICP_METRIC_POINT &&
+      s->reject == ICP_REJECT_SIGMA) {
     std::vector<icp::LoopRec> recs((size_t)icp_hip_ctx::kLoopRing);
     std::vector<double> ms((size_t)icp_hip_ctx::kLoopRing);
     while (n < k && !s->core.done && rc == ICP_HIP_OK) {
@@ -408,11 +454,30 @@ int icp_engine_run(icp_hip_ctx* ctx, const icp_params* p, icp_result* res, icp_i
 
 int icp_engine_run_metric(icp_hip_ctx* ctx, const icp_params* p, int32_t metric, icp_result* res,
                           icp_iteration_record* hist, int32_t cap, const icp_engine_hooks* hooks) {
-  if (!ctx || !p || !res) return ICP_HIP_EINVAL;
+  icp_run_options opt;
+  icp_run_options_default(&opt);
+  opt.metric = metric;
+  return icp_engine_run_options(ctx, p, &opt, res, hist, cap, hooks);
+}
+
+void icp_run_options_default(icp_run_options* opt) {
+  if (!opt) return;
+  opt->version = ICP_RUN_OPTIONS_VERSION;
+  opt->metric = ICP_METRIC_POINT;
+  opt->reject = ICP_REJECT_SIGMA;
+  opt->reject_param = 0.0;
+}
+
+int icp_engine_run_options(icp_hip_ctx* ctx, const icp_params* p, const icp_run_options* opt, icp_result* res,
+                           icp_iteration_record* hist, int32_t cap, const icp_engine_hooks* hooks) {
+  if (!ctx || !p || !res || !opt) return ICP_HIP_EINVAL;
+  if (opt->version != ICP_RUN_OPTIONS_VERSION) return fail(ICP_HIP_EINVAL, "run_options: unknown version");
   icp_session* s = nullptr;
   int rc = icp_session_create(ctx, p, hooks, &s);
   if (rc != ICP_HIP_OK) return rc;
-  if (metric != ICP_METRIC_POINT && (rc = icp_session_set_metric(s, metric)) != ICP_HIP_OK) {
+  if (opt->metric != ICP_METRIC_POINT) rc = icp_session_set_metric(s, opt->metric);
+  if (rc == ICP_HIP_OK && opt->reject != ICP_REJECT_SIGMA) rc = icp_session_set_rejection(s, opt->reject, opt->reject_param);
+  if (rc != ICP_HIP_OK) {
     std::memset(res, 0, sizeof(*res));
     set_msg(res, icp_hip_last_error());
     icp_session_destroy(s);

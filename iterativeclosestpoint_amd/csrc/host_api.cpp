@@ -172,6 +172,11 @@ double icp_cull_threshold(double mean, double sd, double k_sigma, int iter, int 
   return icp::cull_threshold(mean, sd, k_sigma, iter, engine_rules);
 }
 
+int64_t icp_trim_rank(double fraction, int64_t n_finite) {
+  if (!(fraction > 0.0 && fraction <= 1.0) || n_finite < 0) return 0;
+  return icp::trim_rank(fraction, n_finite);
+}
+
 void icp_synth_default(icp_synth_spec* s) {
   s->sigma[0] = 5.0;
   s->sigma[1] = 5.0;

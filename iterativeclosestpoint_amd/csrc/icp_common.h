@@ -154,4 +154,14 @@ ICP_HD double cull_threshold(double mean, double sd, double k_sigma, int iter, i
   return mean + k_sigma * sd;
 }
 
+// The trimmed rejector's rank: the pairs kept of n_finite ranked ones at the fraction kept (in
+// (0, 1]), at least 3 (all of fewer). One fp64 product and one truncation, on the host and on the
+// device: the same bits.
+ICP_HD int64_t trim_rank(double fraction, int64_t n_finite) {
+  const int64_t lo = n_finite < 3 ? n_finite : 3;
+  int64_t k = (int64_t)(fraction * (double)n_finite);
+  k = k < n_finite ? k : n_finite;
+  return lo > k ? lo : k;
+}
+
 }  // namespace icp

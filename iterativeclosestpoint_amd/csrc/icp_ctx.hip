@@ -189,6 +189,7 @@ void icp_hip_destroy(icp_hip_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   prewalk_destroy(c);
   las_destroy(c);
+  reject_destroy(c);
   free_source(c);
   free_target(c);
   dfree(c->it);

@@ -169,6 +169,12 @@ struct icp_hip_ctx {
   double* plane_parts = nullptr;  // plane_cap parts + the merged sums (kPlaneSums doubles each)
   int64_t plane_cap = 0;
 
+  // --- rejectors (ctx_reject.cpp): the select's histograms and states, and the pair sums' parts
+  // (made at first use, released with the context)
+  void* select_buf = nullptr;
+  double* pair_parts = nullptr;  // pair_cap parts, then the merged record and the first-pair word
+  int64_t pair_cap = 0;
+
   // --- voxel-grid down-sampling (ctx_voxel.cpp): the phases' device times of the last call
   double voxel_ms[5] = {0, 0, 0, 0, 0};
   bool voxel_timed = false;
@@ -291,6 +297,9 @@ int prewalk_launch(icp_hip_ctx* c, const icp::NNLaunch& a);  // after launch_nn 
 
 // --- ctx_plane.cpp
 void plane_free_target(icp_hip_ctx* c);  // free_target's part: the normals and the plane sums' buffers
+
+// --- ctx_reject.cpp
+void reject_destroy(icp_hip_ctx* c);  // the rejectors' buffers released (icp_hip_destroy)
 
 // --- ctx_las.cpp
 void las_destroy(icp_hip_ctx* c);  // the staging buffers released (icp_hip_destroy)

@@ -7,7 +7,13 @@
 //                    [--sample-rate 50] [--max-iters 20] [--tolerance 1e-2]
 //                    [--outdir .] [--device 0 | --devices 0,1,...] [--device-io] [--pause]
 //                    [--metric point|plane] [--normals-k 16] [--voxel X]
-//                    [--sor K,RATIO] [--radius-filter R,MIN]
+//                    [--sor K,RATIO] [--radius-filter R,MIN] [--trim F | --max-dist D]
+//
+// --trim F registers with the trimmed rejector (icp_engine_run_options, ICP_REJECT_TRIM): each
+// iteration keeps the fraction F, in (0, 1], of its pairs with the smallest residuals, for scans that
+// overlap only partly. --max-dist D keeps the pairs no farther apart than D metres
+// (ICP_REJECT_MAX_DIST). One of the two at most, alone or with --metric plane; one GPU only. The
+// CLI's rules, decisions and files otherwise. Without the flags every output is unchanged.
 //
 // --voxel X (metres, > 0) reduces each cloud, after the stride sampling, to the centroids of the
 // voxels of edge X of a grid of its own with the origin at the cloud's minimum
@@ -67,6 +73,8 @@ struct Args {
   double sor_ratio = 0.0;
   double radius = 0.0;  // 0: no radius filter
   int radius_min = 0;
+  int reject = ICP_REJECT_SIGMA;  // --trim / --max-dist
+  double reject_param = 0.0;
   bool filtered() const { return sor_k > 0 || radius > 0.0; }
 };
 
@@ -75,7 +83,7 @@ struct Args {
                "usage: %s [--source F] [--target F] [--sample-rate N] [--max-iters N] [--tolerance X]\n"
                "          [--outdir D] [--device N | --devices N,M,...] [--device-io] [--pause]\n"
                "          [--metric point|plane] [--normals-k N] [--voxel X]\n"
-               "          [--sor K,RATIO] [--radius-filter R,MIN]\n",
+               "          [--sor K,RATIO] [--radius-filter R,MIN] [--trim F | --max-dist D]\n",
                prog);
   std::exit(code);
 }
@@ -129,6 +137,22 @@ Args parse(int argc, char** argv) {
       }
       a.radius_min = (int)mm;
     }
+    else if (k == "--trim" || k == "--max-dist") {
+      const bool trim = k == "--trim";
+      const char* v = val();
+      char* end = nullptr;
+      const double x = std::strtod(v, &end);
+      if (a.reject != ICP_REJECT_SIGMA) {
+        std::fprintf(stderr, "--trim and --max-dist: one rejector at most\n");
+        usage(argv[0], 2);
+      }
+      if (end == v || *end != '\0' || !(x > 0.0) || (trim ? !(x <= 1.0) : !(x - x == 0.0))) {
+        std::fprintf(stderr, trim ? "--trim must be a fraction in (0, 1]\n" : "--max-dist must be a finite distance > 0 (metres)\n");
+        usage(argv[0], 2);
+      }
+      a.reject = trim ? ICP_REJECT_TRIM : ICP_REJECT_MAX_DIST;
+      a.reject_param = x;
+    }
     else if (k == "--max-iters") a.max_iters = (int)std::strtol(val(), nullptr, 10);
     else if (k == "--tolerance") a.tolerance = std::strtod(val(), nullptr);
     else if (k == "--outdir") a.outdir = val();
@@ -171,6 +195,10 @@ Args parse(int argc, char** argv) {
   }
   if (a.metric == ICP_METRIC_PLANE && a.devices.size() > 1) {
     std::fprintf(stderr, "--metric plane runs on one GPU (the plane sums are not exchanged between devices)\n");
+    usage(argv[0], 2);
+  }
+  if (a.reject != ICP_REJECT_SIGMA && a.devices.size() > 1) {
+    std::fprintf(stderr, "--trim and --max-dist run on one GPU (the residuals are not exchanged between devices)\n");
     usage(argv[0], 2);
   }
   if (a.metric == ICP_METRIC_PLANE && (a.normals_k < 3 || a.normals_k > ICP_HIP_KNN_MAX)) {
@@ -323,6 +351,21 @@ icp_params cli_params(const Args& a) {
   return p;
 }
 
+// The run's options of the flags, and the line that names a rejector.
+icp_run_options cli_options(const Args& a) {
+  icp_run_options o;
+  icp_run_options_default(&o);
+  o.metric = a.metric;
+  o.reject = a.reject;
+  o.reject_param = a.reject_param;
+  return o;
+}
+
+void print_rejector(const Args& a) {
+  if (a.reject == ICP_REJECT_TRIM) std::cout << "rejector: trimmed, keeps " << a.reject_param << " of the pairs" << std::endl;
+  if (a.reject == ICP_REJECT_MAX_DIST) std::cout << "rejector: pairs within " << a.reject_param << " m" << std::endl;
+}
+
 // The per-iteration transforms of a run's history, the first cap of them into out; *n_tr counts all.
 void collect_transforms(const icp_result& res, const std::vector<icp_iteration_record>& hist, int32_t cap, double* out,
                         int32_t* n_tr) {
@@ -409,7 +452,10 @@ int run_device_io(const Args& a) {
     std::cout << "metric: point-to-plane, normals from " << a.normals_k << " neighbours" << std::endl;
     if (icp_hip_estimate_target_normals(ctx, a.normals_k, nullptr) != ICP_HIP_OK) return bail("cannot estimate the target normals");
   }
-  const int rc = icp_engine_run_metric(ctx, &p, a.metric, &res, hist.data(), cap, nullptr);
+  print_rejector(a);
+  const icp_run_options opt = cli_options(a);
+  const int rc = a.reject == ICP_REJECT_SIGMA ? icp_engine_run_metric(ctx, &p, a.metric, &res, hist.data(), cap, nullptr)
+                                              : icp_engine_run_options(ctx, &p, &opt, &res, hist.data(), cap, nullptr);
   if (rc != ICP_HIP_OK) {
     std::cerr << "ICP failed (" << rc << ")";
     return bail("registration failed");
@@ -433,9 +479,9 @@ int run_device_io(const Args& a) {
   return 0;
 }
 
-// ICP() with the point-to-plane step on host clouds: icp_cli_icp_devices' steps on one context, with
-// the normals estimated once the target is set. src is moved in place.
-int cli_icp_plane(const Args& a, double* src, int64_t ns, const double* tgt, int64_t nt, double R[9], double t[3],
+// ICP() with the point-to-plane step or a rejector on host clouds: icp_cli_icp_devices' steps on one
+// context, with the normals (plane metric) estimated once the target is set. src is moved in place.
+int cli_icp_options(const Args& a, double* src, int64_t ns, const double* tgt, int64_t nt, double R[9], double t[3],
                   double* transforms, int32_t cap, int32_t* n_tr) {
   const icp_params p = cli_params(a);
   std::vector<icp_iteration_record> hist((size_t)cap);
@@ -443,9 +489,12 @@ int cli_icp_plane(const Args& a, double* src, int64_t ns, const double* tgt, int
   icp_hip_ctx* ctx = nullptr;
   int rc = icp_hip_create(&ctx, a.devices[0]);
   if (rc == ICP_HIP_OK) rc = icp_hip_set_target(ctx, tgt, nt, 10, 20, ICP_RULES_CLI);
-  if (rc == ICP_HIP_OK) rc = icp_hip_estimate_target_normals(ctx, a.normals_k, nullptr);
+  if (rc == ICP_HIP_OK && a.metric == ICP_METRIC_PLANE) rc = icp_hip_estimate_target_normals(ctx, a.normals_k, nullptr);
   if (rc == ICP_HIP_OK) rc = icp_hip_set_source(ctx, src, ns);
-  if (rc == ICP_HIP_OK) rc = icp_engine_run_metric(ctx, &p, ICP_METRIC_PLANE, &res, hist.data(), cap, nullptr);
+  const icp_run_options opt = cli_options(a);
+  if (rc == ICP_HIP_OK)
+    rc = a.reject == ICP_REJECT_SIGMA ? icp_engine_run_metric(ctx, &p, a.metric, &res, hist.data(), cap, nullptr)
+                                      : icp_engine_run_options(ctx, &p, &opt, &res, hist.data(), cap, nullptr);
   if (rc == ICP_HIP_OK) rc = icp_hip_get_source(ctx, src);
   icp_hip_destroy(ctx);
   if (rc != ICP_HIP_OK) return rc;
@@ -514,8 +563,9 @@ int main(int argc, char** argv) {
   if (a.devices.size() > 1) std::cout << "devices: " << a.devices.size() << " GPUs" << std::endl;
   if (a.metric == ICP_METRIC_PLANE)
     std::cout << "metric: point-to-plane, normals from " << a.normals_k << " neighbours" << std::endl;
-  const int rc = a.metric == ICP_METRIC_PLANE
-                     ? cli_icp_plane(a, ss.data(), ns, ts.data(), nt, R, t, transforms.data(), cap, &n_tr)
+  print_rejector(a);
+  const int rc = a.metric == ICP_METRIC_PLANE || a.reject != ICP_REJECT_SIGMA
+                     ? cli_icp_options(a, ss.data(), ns, ts.data(), nt, R, t, transforms.data(), cap, &n_tr)
                      : icp_cli_icp_devices(ss.data(), ns, ts.data(), nt, a.max_iters, a.tolerance, R, t, transforms.data(),
                                            cap, &n_tr, (int)a.devices.size(), a.devices.data());
   if (rc != 0) {

@@ -249,9 +249,54 @@ struct PlaneLaunch {
   int64_t n;
   double* parts;  // plane_num_parts(n) x kPlaneSums
   double* out;    // kPlaneSums
+  double thr;     // launch_plane_sums_at: the caller's threshold (it is not read)
 };
 int64_t plane_num_parts(int64_t n);
 hipError_t launch_plane_sums(const PlaneLaunch& a, hipStream_t s);
+// The same sums over the pairs with a finite d <= a.thr.
+hipError_t launch_plane_sums_at(const PlaneLaunch& a, hipStream_t s);
+
+// --- reject_kernels.hip: the rank select over the residuals and the pair sums at a caller's
+// threshold.
+constexpr int kSelectPasses = 6;   // 11-bit digits of the 64-bit key, the last one 9 bits
+constexpr int kSelectBins = 2048;
+enum : unsigned { kSelectOk = 0, kSelectEmpty = 1, kSelectRange = 2 };  // no finite residual; rank > n_finite
+// The select's device-resident record: the state after each digit, and after the last the result.
+struct SelectState {
+  unsigned long long key;        // the selected key's resolved digits (after the last: the value's bits)
+  unsigned long long rank_left;  // the rank inside the bucket of the resolved digits (1-based)
+  unsigned long long n_less;     // finite residuals below that bucket
+  unsigned long long n_finite;
+  unsigned long long rank;       // the rank the call selects
+  unsigned long long n_equal;    // residuals in the bucket (after the last digit: equal to the value)
+  unsigned long long status;     // kSelect*
+  unsigned long long pad;
+};
+size_t select_scratch_bytes();  // the histograms and the states of one call
+const SelectState* select_result(const void* scratch);  // where the finished call's record lies (device)
+int select_full_reads();        // passes over the residuals of one call
+// The rank-th smallest finite residual of dist[0, n): rank >= 1, or (rank 0) trim_rank(fraction,
+// n_finite) computed on the device once the first pass has counted n_finite. Chained on s, no host
+// wait; the result is *select_result(scratch).
+hipError_t launch_residual_select(const double* dist, int64_t n, double fraction, int64_t rank, void* scratch,
+                                  hipStream_t s);
+
+constexpr int kPairRec = 20;  // doubles per part of the pair sums (the CovMoments record's size)
+struct PairLaunch {
+  const double* x;
+  const double* y;
+  const double* z;
+  const int32_t* pos;
+  const double* dist;
+  const TgtPt* pts;
+  double thr;
+  int64_t n;
+  unsigned* first;  // scratch: the lowest index of a valid pair
+  double* parts;    // pair_num_parts(n) x kPairRec
+  double* out;      // kPairRec + 1: the valid pairs' CovMoments, then the finite residuals
+};
+int64_t pair_num_parts(int64_t n);
+hipError_t launch_pair_sums(const PairLaunch& a, hipStream_t s);
 
 // --- voxel_kernels.hip: voxel-grid down-sampling (the definition: voxel_host.h).
 struct VoxelOrigin {

@@ -1,7 +1,7 @@
 // plane_kernels.hip — the point-to-plane normal equations of an iterate's valid pairs (DESIGN.md
 // §3.9), fp64, no FMA. A call of its own after the iterate: it reads the moved source, the matches,
-// the residuals, the device record's threshold, the target points and the normals at the matches,
-// and writes none of them.
+// the residuals, the device record's threshold (or the caller's: launch_plane_sums_at), the target
+// points and the normals at the matches, and writes none of them.
 //  k_plane_sums   fixed parts of 4096 queries (as k_moments): thread t of a part adds its queries
 //                 t + 256 j (j < 16) in order, then the block's fixed tree (block_sum).
 //  k_plane_merge  the parts added in index order, one thread per sum.
@@ -18,10 +18,12 @@ using namespace dev;
 constexpr int kPlanePart = 4096;
 constexpr int kPlaneBlock = 256;
 
+// AT: the caller's threshold (a.thr) and only finite residuals, instead of the device record's.
+template <bool AT>
 __global__ void __launch_bounds__(kPlaneBlock) k_plane_sums(PlaneLaunch a) {
   __shared__ double red[(kPlaneBlock / kWave) * kPlaneSums];
   const int64_t base = (int64_t)blockIdx.x * kPlanePart;
-  const double thr = a.it->thr;
+  const double thr = AT ? a.thr : a.it->thr;
   const double ox = a.origin[0], oy = a.origin[1], oz = a.origin[2];
   double v[kPlaneSums];
 #pragma unroll
@@ -31,6 +33,7 @@ __global__ void __launch_bounds__(kPlaneBlock) k_plane_sums(PlaneLaunch a) {
     if (i >= a.n) break;
     const double d = a.dist[i];
     if (!(d <= thr)) continue;  // the cull's rule (icpengine.cpp:265); a NaN residual is invalid
+    if (AT && !__builtin_isfinite(d)) continue;  // an infinite threshold takes every finite pair
     const int32_t pos = a.pos[i];
     const double nx = a.normals[3 * (int64_t)pos], ny = a.normals[3 * (int64_t)pos + 1],
                  nz = a.normals[3 * (int64_t)pos + 2];
@@ -79,11 +82,17 @@ __global__ void __launch_bounds__(64) k_plane_merge(const double* __restrict__ p
 
 int64_t plane_num_parts(int64_t n) { return (n + kPlanePart - 1) / kPlanePart; }
 
-hipError_t launch_plane_sums(const PlaneLaunch& a, hipStream_t s) {
+namespace {
+template <bool AT>
+hipError_t launch_plane(const PlaneLaunch& a, hipStream_t s) {
   const int64_t nparts = plane_num_parts(a.n);
-  if (nparts > 0) hipLaunchKernelGGL(k_plane_sums, dim3((unsigned)nparts), dim3(kPlaneBlock), 0, s, a);
+  if (nparts > 0) hipLaunchKernelGGL(k_plane_sums<AT>, dim3((unsigned)nparts), dim3(kPlaneBlock), 0, s, a);
   hipLaunchKernelGGL(k_plane_merge, dim3(1), dim3(64), 0, s, a.parts, nparts, a.out);
   return hipGetLastError();
 }
+}  // namespace
+
+hipError_t launch_plane_sums(const PlaneLaunch& a, hipStream_t s) { return launch_plane<false>(a, s); }
+hipError_t launch_plane_sums_at(const PlaneLaunch& a, hipStream_t s) { return launch_plane<true>(a, s); }
 
 }  // namespace icp
