@@ -471,8 +471,10 @@ int icp_hip_knn_device(icp_hip_ctx* ctx, const double* d_q_xyz, int64_t n, int k
  * neighbour order, C = sum (p_i - m)(p_i - m)^T in fp64, the normal the unit eigenvector of C's
  * smallest eigenvalue. Sign: with a viewpoint v (double[3]) n.(v - p) >= 0; with null the component of
  * largest magnitude is positive (ties: the lowest axis). A neighbourhood whose C has fewer than two
- * positive eigenvalues (copies, collinear points) gets the normal (0, 0, 0). icp_hip_set_target drops
- * the normals. */
+ * eigenvalues above 2^-26 of the largest (copies, collinear points: their second eigenvalue is the
+ * sums' rounding, seldom exactly zero) gets the normal (0, 0, 0); 2^-26 is sqrt(eps), below it the
+ * direction keeps fewer than half its digits (an aspect ratio of 1.2e-4, far below a scan's grid).
+ * icp_hip_set_target drops the normals. */
 int icp_hip_estimate_target_normals(icp_hip_ctx* ctx, int k, const double* viewpoint);
 /* Normals the caller already has, in the caller's target order (n_tgt x 3). Every row is of unit
  * length (|n.n - 1| <= 1e-12) or zero, else ICP_HIP_EINVAL and the context's normals stay as they were. */

@@ -41,6 +41,11 @@ __global__ void __launch_bounds__(256) k_knn(const NodeRec* __restrict__ nodes, 
   }
 }
 
+// A neighbourhood defines a plane only when its second eigenvalue is above this fraction of the
+// first (sqrt(eps), as kPlanePivotMin): below it the smallest eigenvector keeps fewer than half
+// its digits, and on collinear points it is made of the sums' rounding. A guard, not a tuned value.
+constexpr double kNormalRankMin = 0x1p-26;
+
 struct View {
   double v[3];
 };
@@ -82,7 +87,7 @@ __global__ void __launch_bounds__(256) k_target_normals(const NodeRec* __restric
   // C is symmetric positive semi-definite: its singular values are its eigenvalues (descending)
   // and V's third column the eigenvector of the smallest
   double nx = 0.0, ny = 0.0, nz = 0.0;
-  if (S[1] > 0.0) {
+  if (S[1] > kNormalRankMin * S[0]) {
     nx = V[2];
     ny = V[5];
     nz = V[8];

@@ -79,12 +79,16 @@ def test_degenerate_neighbourhoods(icp):
     zero = (nrm == 0.0).all(1)
     # by the definition of the neighbours (smallest (d2, index)): every copy's 8 neighbours are the 8
     # copies of lowest index, so every copy's neighbourhood is one point; the copies with at least
-    # 8 copies of lower or equal index are among them, and no other point has a zero normal
+    # 8 copies of lower or equal index are among them. A point whose other seven neighbours are all
+    # copies has two distinct points for a neighbourhood, a line (S[1] is the sums' rounding, 1e-19
+    # here, not zero). No other point has a zero normal
     idx, d2 = pf.knn_brute(tgt, tgt, 8)
-    want = (d2 == 0.0).all(1)
-    assert np.array_equal(np.flatnonzero(want), where)
+    copies = (d2 == 0.0).all(1)
+    assert np.array_equal(np.flatnonzero(copies), where)
     assert zero[where[7:]].all()
-    assert np.array_equal(zero, want)
+    two = np.array([len(np.unique(tgt[r], axis=0)) == 2 for r in idx])
+    assert np.array_equal(np.flatnonzero(two), [3, 560])
+    assert np.array_equal(zero, copies | two)
     assert np.abs(np.linalg.norm(nrm[~zero], axis=1) - 1.0).max() <= 1e-14
 
 
