@@ -129,13 +129,24 @@ int icp_session_step_n_timed(icp_session* s, int32_t k, int32_t* steps_done, int
  * icp_plane_solve; an iteration whose solve refuses takes the SVD step instead. A plane session
  * steps on the host (never the device-resident loop) and needs normals on the context
  * (ICP_HIP_ENOTREADY without them; ICP_HIP_EINVAL on a multi-device context or one with a
- * communicator). Call it before the first step: later it returns ICP_HIP_EINVAL. */
+ * communicator). Call it before the first step: later it returns ICP_HIP_EINVAL.
+ * ICP_METRIC_GICP is generalized ICP ("plane-to-plane", icp_hip.h): the same decisions again, the
+ * increment from icp_hip_gicp_sums about the iterate's centroid_src with the context's epsilon
+ * (icp_hip_set_gicp_epsilon) and R_src = the rotation of the session's cumulative transform before
+ * the step, then icp_gicp_solve, and the SVD step when the solve refuses. It steps on the host and
+ * needs normals of the target and of the source (ICP_HIP_ENOTREADY without either, and when the
+ * resident source has been moved since its normals were made: they are in the frame of that
+ * moment, which must be the session's start); ICP_HIP_EINVAL on a multi-device context or one with
+ * a communicator. */
 #define ICP_METRIC_POINT 0
 #define ICP_METRIC_PLANE 1
+#define ICP_METRIC_GICP 2
 int icp_session_set_metric(icp_session* s, int32_t metric);
 /* The last step of a plane session: its sums (zeros when the step computed none: a stop, or a
  * point session) and whether the plane solve gave the increment. Either output may be null. */
 int icp_session_last_plane(const icp_session* s, icp_plane_sums* out, int32_t* used_plane);
+/* The same for a generalized-ICP session. */
+int icp_session_last_gicp(const icp_session* s, icp_gicp_sums* out, int32_t* used);
 /* icp_engine_run with a metric. */
 int icp_engine_run_metric(icp_hip_ctx* ctx, const icp_params* p, int32_t metric, icp_result* res,
                           icp_iteration_record* history, int32_t history_cap, const icp_engine_hooks* hooks);
@@ -150,7 +161,8 @@ int icp_engine_run_metric(icp_hip_ctx* ctx, const icp_params* p, int32_t metric,
  *   4. takes the loop's decisions (convergence, divergence, too few) and the best fit from that
  *      call's rmse, valid, centroids and H in place of the cull's, by the same code.
  * With ICP_METRIC_PLANE a step that fits takes icp_hip_plane_sums_at(origin = the pair sums'
- * centroid_src, t), then icp_plane_solve, and the SVD increment when the solve refuses. The record of
+ * centroid_src, t), then icp_plane_solve, and the SVD increment when the solve refuses; with
+ * ICP_METRIC_GICP icp_hip_gicp_sums_at and icp_gicp_solve in the same way. The record of
  * the iteration carries t as threshold, the rejector's valid_points, outlier_points and rmse, and the
  * iterate's own mean and std. Such a session steps on the host (never the device-resident loop).
  * Call it before the first step: later it returns ICP_HIP_EINVAL, as it does for another mode, a

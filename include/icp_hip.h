@@ -558,6 +558,66 @@ int icp_hip_pair_sums(icp_hip_ctx* ctx, double threshold, icp_pair_sums* out);
  * ICP_HIP_EINVAL for a NaN threshold or a non-finite origin. */
 int icp_hip_plane_sums_at(icp_hip_ctx* ctx, const double origin[3], double threshold, icp_plane_sums* out);
 
+/* --- Generalized ICP, "plane-to-plane" (DESIGN.md §3.13): normals on the source and the sums that
+ * weight each pair by the local surface of both clouds. Beside the reference's loop: nothing here
+ * changes what the calls above compute. With the plane regularisation a point's covariance is
+ * C = I - (1 - epsilon) n n^T for its unit normal n (C = I for a zero normal), so normals are all
+ * that is stored. All of it is ICP_HIP_EINVAL on a multi-device context and on one with a
+ * communicator (the source is sharded, the sums are not exchanged). */
+
+/* One normal per source point by icp_hip_estimate_target_normals' rule, word for word, over the
+ * resident source as it stands at the call: the k nearest source points under (fl(d2), index in the
+ * caller's source order), the mean in neighbour order, the centred moments, the 2^-26 rank rule and
+ * the sign rules (viewpoint, or largest component positive). The bytes are those the same cloud gets
+ * as a target. ICP_HIP_EINVAL: k outside [3, ICP_HIP_KNN_MAX] or above the source size, a non-finite
+ * viewpoint, a resident source with a non-finite coordinate (the text says how many; such a source
+ * can be given normals with icp_hip_set_source_normals). ICP_HIP_ENOTREADY without a source.
+ * The normals are in the frame the source had when they were made: nothing rotates them, and
+ * icp_hip_gicp_sums takes the rotation since then as R_src. icp_hip_set_source (every variant) drops them. */
+int icp_hip_estimate_source_normals(icp_hip_ctx* ctx, int k, const double* viewpoint);
+/* Normals the caller already has, in the caller's source order (n_src x 3). Every row is of unit
+ * length (|n.n - 1| <= 1e-12) or zero, else ICP_HIP_EINVAL and the context's normals stay as they were. */
+int icp_hip_set_source_normals(icp_hip_ctx* ctx, const double* n_xyz);
+int icp_hip_set_source_normals_device(icp_hip_ctx* ctx, const double* d_n_xyz);
+/* The source's normals in the caller's source order; ICP_HIP_ENOTREADY when there are none. */
+int icp_hip_get_source_normals(icp_hip_ctx* ctx, double* n_xyz_out);
+int icp_hip_get_source_normals_device(icp_hip_ctx* ctx, double* d_n_xyz_out);
+
+/* The generalized-ICP normal equations of the last iterate's valid pairs (the pairs icp_hip_plane_sums
+ * selects; none is left out for a zero normal). Per pair, with a the moved source point, b its match,
+ * na = R_src n0 the source normal in a's frame, nb the target normal: S = C_a + C_b, M = S^-1,
+ * r = a - b, a' = a - origin, J = [-[a']x | I]: A = sum J^T M J (6 x 6, symmetric, row-major),
+ * g = sum J^T M r, sum_r2 = sum r^T M r; n the pairs summed, n_iso_src / n_iso_tgt those of them
+ * with a zero source / target normal. */
+typedef struct icp_gicp_sums {
+  double A[36];
+  double g[6];
+  double sum_r2;
+  int64_t n;
+  int64_t n_iso_src, n_iso_tgt;
+  double origin[3];
+  double epsilon;
+} icp_gicp_sums;
+
+/* The sums, after icp_hip_iterate on a context with target and source normals. R_src (row-major
+ * 3 x 3) is the rotation the resident source has undergone since its normals were made. Reads what
+ * the iterate left resident and writes none of it. Deterministic as icp_hip_plane_sums: fixed parts
+ * of 4096 queries, a fixed tree inside a part, the parts added in index order; one host wait.
+ * ICP_HIP_EINVAL: a null argument, a non-finite origin, an R_src with a non-finite entry or with
+ * |R R^T - I| above 1e-9 in an entry, epsilon outside [2^-20, 1], a NaN threshold (+inf takes every
+ * finite pair). ICP_HIP_ENOTREADY: no target, no target normals, no source normals, no iterate yet on
+ * this source. All before any kernel runs. */
+int icp_hip_gicp_sums(icp_hip_ctx* ctx, const double origin[3], const double R_src[9], double epsilon,
+                      icp_gicp_sums* out);
+int icp_hip_gicp_sums_at(icp_hip_ctx* ctx, const double origin[3], const double R_src[9], double epsilon,
+                         double threshold, icp_gicp_sums* out);
+
+/* The step from the sums (host, no GPU): icp_plane_solve on A, g, n and origin, with the same refusals. */
+void icp_gicp_solve(const icp_gicp_sums* sums, double T[16], int32_t* ok);
+
+/* The epsilon of the context's generalized-ICP sessions (icp_engine.h): default 1e-3, in [2^-20, 1]. */
+int icp_hip_set_gicp_epsilon(icp_hip_ctx* ctx, double epsilon);
+
 /* --- Voxel-grid down-sampling. Beside everything above: it needs no target and no
  * source and touches neither.
  * n points (AoS xyz, fp64), a voxel edge `voxel` and an origin o: the caller's, or with null the

@@ -27,7 +27,7 @@ XPORT_CALLBACK = 3
 OK, EINVAL, ENOMEM, EDEVICE, ERCCL, ENOTREADY, EEXCHANGE = 0, -1, -2, -3, -4, -5, -6
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2  # icp_hip_dev_copy directions
 DBG_SLOTS = 40
-METRIC_POINT, METRIC_PLANE = 0, 1  # icp_engine.h ICP_METRIC_*
+METRIC_POINT, METRIC_PLANE, METRIC_GICP = 0, 1, 2  # icp_engine.h ICP_METRIC_*
 REJECT_SIGMA, REJECT_TRIM, REJECT_MAX_DIST = 0, 1, 2  # icp_engine.h ICP_REJECT_*
 RUN_OPTIONS_VERSION = 1  # icp_engine.h ICP_RUN_OPTIONS_VERSION
 KNN_MAX = 32
@@ -164,6 +164,14 @@ class PlaneSums(C.Structure):
     ]
 
 
+class GicpSums(C.Structure):
+    """icp_gicp_sums (include/icp_hip.h): the generalized-ICP normal equations of an iterate."""
+    _fields_ = [
+        ("A", C.c_double * 36), ("g", C.c_double * 6), ("sum_r2", C.c_double), ("n", C.c_int64),
+        ("n_iso_src", C.c_int64), ("n_iso_tgt", C.c_int64), ("origin", C.c_double * 3), ("epsilon", C.c_double),
+    ]
+
+
 class SelectResult(C.Structure):
     """icp_select_result (include/icp_hip.h): a rank select over the last iterate's residuals."""
     _fields_ = [("value", C.c_double), ("rank", C.c_int64), ("n_finite", C.c_int64), ("n_less", C.c_int64),
@@ -231,6 +239,15 @@ SIGNATURES = {
     "icp_hip_residual_select": (C.c_int, [_P, C.c_double, C.c_int64, C.POINTER(SelectResult)]),
     "icp_hip_pair_sums": (C.c_int, [_P, C.c_double, C.POINTER(PairSums)]),
     "icp_hip_plane_sums_at": (C.c_int, [_P, _P, C.c_double, C.POINTER(PlaneSums)]),
+    "icp_hip_estimate_source_normals": (C.c_int, [_P, C.c_int, _P]),
+    "icp_hip_set_source_normals": (C.c_int, [_P, _P]),
+    "icp_hip_set_source_normals_device": (C.c_int, [_P, _P]),
+    "icp_hip_get_source_normals": (C.c_int, [_P, _P]),
+    "icp_hip_get_source_normals_device": (C.c_int, [_P, _P]),
+    "icp_hip_gicp_sums": (C.c_int, [_P, _P, _P, C.c_double, C.POINTER(GicpSums)]),
+    "icp_hip_gicp_sums_at": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.POINTER(GicpSums)]),
+    "icp_gicp_solve": (None, [C.POINTER(GicpSums), _P, _I32]),
+    "icp_hip_set_gicp_epsilon": (C.c_int, [_P, C.c_double]),
     "icp_hip_voxel_downsample": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, C.c_int, C.c_int64, _P, _P, _P,
                                            C.POINTER(C.c_int64), _P]),
     "icp_hip_voxel_downsample_device": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, C.c_int, C.c_int64, _P, _P, _P,
@@ -275,6 +292,7 @@ SIGNATURES = {
     "icp_session_finish": (C.c_int, [_P, C.POINTER(Result)]),
     "icp_session_set_metric": (C.c_int, [_P, C.c_int32]),
     "icp_session_last_plane": (C.c_int, [_P, C.POINTER(PlaneSums), _I32]),
+    "icp_session_last_gicp": (C.c_int, [_P, C.POINTER(GicpSums), _I32]),
     "icp_engine_run_metric": (C.c_int, [_P, C.POINTER(Params), C.c_int32, C.POINTER(Result),
                                         C.POINTER(IterationRecord), C.c_int32, C.POINTER(Hooks)]),
     "icp_session_set_rejection": (C.c_int, [_P, C.c_int32, C.c_double]),
@@ -609,6 +627,50 @@ class Context:
         out = PlaneSums()
         _check(lib().icp_hip_plane_sums_at(self._h, _ptr(o), threshold, C.byref(out)))
         return out
+
+    # --- generalized ICP (include/icp_hip.h): source normals and the plane-to-plane sums
+    def estimate_source_normals(self, k: int = 16, viewpoint=None):
+        v = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float64).reshape(3)
+        _check(lib().icp_hip_estimate_source_normals(self._h, k, _ptr(v)))
+
+    def set_source_normals(self, n_xyz):
+        """Normals in the caller's source order: a DeviceBuffer / device address, or an (n, 3) array."""
+        if isinstance(n_xyz, (DeviceBuffer, int)):
+            _check(lib().icp_hip_set_source_normals_device(self._h, _dptr(n_xyz)))
+            return
+        n_xyz = _aos(n_xyz)
+        if n_xyz.shape[0] != self.n_src:
+            raise ValueError("one normal per source point")
+        _check(lib().icp_hip_set_source_normals(self._h, _ptr(n_xyz)))
+
+    def get_source_normals(self, d_out=None):
+        """The source's normals, caller's order: an (n, 3) array, or written to the device buffer d_out."""
+        if d_out is not None:
+            _check(lib().icp_hip_get_source_normals_device(self._h, _dptr(d_out)))
+            return d_out
+        out = np.empty((self.n_src, 3), np.float64)
+        _check(lib().icp_hip_get_source_normals(self._h, _ptr(out)))
+        return out
+
+    def gicp_sums(self, origin=(0.0, 0.0, 0.0), R_src=None, epsilon: float = 1e-3) -> GicpSums:
+        """The generalized-ICP sums of the last iterate's valid pairs about `origin`; R_src (3, 3):
+        the rotation of the resident source since its normals were made (default: none)."""
+        o = np.ascontiguousarray(origin, np.float64).reshape(3)
+        R = np.ascontiguousarray(np.eye(3) if R_src is None else R_src, np.float64).reshape(9)
+        out = GicpSums()
+        _check(lib().icp_hip_gicp_sums(self._h, _ptr(o), _ptr(R), epsilon, C.byref(out)))
+        return out
+
+    def gicp_sums_at(self, origin, R_src, epsilon: float, threshold: float) -> GicpSums:
+        """gicp_sums over the pairs with a finite d <= threshold."""
+        o = np.ascontiguousarray(origin, np.float64).reshape(3)
+        R = np.ascontiguousarray(np.eye(3) if R_src is None else R_src, np.float64).reshape(9)
+        out = GicpSums()
+        _check(lib().icp_hip_gicp_sums_at(self._h, _ptr(o), _ptr(R), epsilon, threshold, C.byref(out)))
+        return out
+
+    def set_gicp_epsilon(self, epsilon: float):
+        _check(lib().icp_hip_set_gicp_epsilon(self._h, epsilon))
 
     # --- voxel-grid down-sampling (include/icp_hip.h; the host's: voxel_downsample below)
     def voxel_downsample(self, xyz, voxel, origin=None, mode=VOXEL_CENTROID, cap=None, count_only=False):
@@ -983,13 +1045,19 @@ class Session:
         _check(lib().icp_session_set_rejection(self._h, mode, param))
 
     def set_metric(self, metric: int):
-        """ICP_METRIC_POINT / ICP_METRIC_PLANE, before the first step (icp_session_set_metric)."""
+        """ICP_METRIC_POINT / _PLANE / _GICP, before the first step (icp_session_set_metric)."""
         _check(lib().icp_session_set_metric(self._h, metric))
 
     def last_plane(self):
         """(sums, used_plane) of the last step of a plane session (icp_session_last_plane)."""
         out, used = PlaneSums(), C.c_int32(0)
         _check(lib().icp_session_last_plane(self._h, C.byref(out), C.byref(used)))
+        return out, used.value
+
+    def last_gicp(self):
+        """(sums, used) of the last step of a generalized-ICP session (icp_session_last_gicp)."""
+        out, used = GicpSums(), C.c_int32(0)
+        _check(lib().icp_session_last_gicp(self._h, C.byref(out), C.byref(used)))
         return out, used.value
 
     def step(self):
@@ -1052,8 +1120,8 @@ def engine_register(params: Params, src, tgt, device: int = -1, history_cap: int
     stop_at >= 0 raises the stop flag from the progress hook of that iteration (the reference's
     cross-thread ICPEngine::stop(), checked at the next iteration, icpengine.cpp:160).
     metric / reject = (mode, param): the registration's steps on one context through
-    icp_engine_run_options (one device, no hooks; the plane metric's normals from normals_k
-    neighbours); the source is written back when the run finished, as the engine does."""
+    icp_engine_run_options (one device, no hooks; the plane and generalized-ICP metrics' normals
+    from normals_k neighbours); the source is written back when the run finished, as the engine does."""
     src = _aos(src).copy()
     tgt = _aos(tgt)
     if metric != METRIC_POINT or reject is not None:
@@ -1061,9 +1129,11 @@ def engine_register(params: Params, src, tgt, device: int = -1, history_cap: int
         with Context(device if devices is None else devices[0]) as ctx:
             ctx.set_target(tgt, 10 if cli else params.octree_max_points, 20 if cli else params.octree_max_depth,
                            params.rules)
-            if metric == METRIC_PLANE:
+            if metric in (METRIC_PLANE, METRIC_GICP):
                 ctx.estimate_target_normals(normals_k)
             ctx.set_source(src)
+            if metric == METRIC_GICP:
+                ctx.estimate_source_normals(normals_k)
             rc, res, hist = ctx.run(params, history_cap, metric=metric,
                                     reject=reject if reject is not None else (REJECT_SIGMA, 0.0))
             if rc == 0:
@@ -1199,6 +1269,14 @@ def plane_solve(sums: PlaneSums):
     T = np.full(16, np.nan)
     ok = C.c_int32(0)
     lib().icp_plane_solve(C.byref(sums), _ptr(T), C.byref(ok))
+    return T.reshape(4, 4), ok.value
+
+
+def gicp_solve(sums: GicpSums):
+    """The generalized-ICP step of the sums (icp_gicp_solve): (T (4, 4), ok), as plane_solve."""
+    T = np.full(16, np.nan)
+    ok = C.c_int32(0)
+    lib().icp_gicp_solve(C.byref(sums), _ptr(T), C.byref(ok))
     return T.reshape(4, 4), ok.value
 
 

@@ -15,6 +15,7 @@ using namespace icp;
 
 void free_source(icp_hip_ctx* c) {
   prewalk_free_source(c);
+  gicp_free_source(c);  // normals name the points of this source
   dfree(c->x);
   dfree(c->y);
   dfree(c->z);
@@ -539,6 +540,7 @@ int icp_hip_apply(icp_hip_ctx* c, const double* T) {
   if (c->group) return group_apply(c, T);
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(launch_apply(T, c->x, c->y, c->z, c->n_src, c->stream));
+  c->src_moves++;
   c->have_prev = false;  // queries moved without a search: previous residuals are no guess
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ICP_HIP_OK;

@@ -210,6 +210,7 @@ static int enqueue_iterate(icp_hip_ctx* c, const double* T_apply, bool apply, in
   if ((rc = clear_and_time(c, a, slot, s)) != ICP_HIP_OK) return rc;
   const bool prewalk = prewalk_arm(c, a, loop, apply);
   HIP_TRY(launch_nn(a, s));
+  if (apply) c->src_moves++;  // the search moves the resident source (a device-loop iterate: may move it)
   if (prewalk && (rc = prewalk_launch(c, a)) != ICP_HIP_OK) return rc;
   const bool multi = c->comm != nullptr || c->xfn != nullptr;
   if (multi && c->inject_failure == 1) {  // testing hook: fail before joining the exchange

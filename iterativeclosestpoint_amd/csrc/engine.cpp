@@ -103,6 +103,8 @@ struct icp_session {
   int32_t metric = ICP_METRIC_POINT;
   icp_plane_sums plane{};  // the last step's sums (plane metric)
   int32_t used_plane = 0;  // the last step's increment came from the plane solve
+  icp_gicp_sums gicp{};    // the last step's sums (generalized-ICP metric)
+  int32_t used_gicp = 0;   // the last step's increment came from the generalized-ICP solve
   int32_t reject = ICP_REJECT_SIGMA;
   double reject_param = 0.0;  // TRIM: the fraction kept; MAX_DIST: the largest residual of a valid pair
 };
@@ -131,13 +133,25 @@ int icp_session_create(icp_hip_ctx* ctx, const icp_params* p, const icp_engine_h
 void icp_session_destroy(icp_session* s) { delete s; }
 
 int icp_session_set_metric(icp_session* s, int32_t metric) {
-  if (!s || (metric != ICP_METRIC_POINT && metric != ICP_METRIC_PLANE)) return fail(ICP_HIP_EINVAL, "set_metric: bad arguments");
+  if (!s || (metric != ICP_METRIC_POINT && metric != ICP_METRIC_PLANE && metric != ICP_METRIC_GICP))
+    return fail(ICP_HIP_EINVAL, "set_metric: bad arguments");
   if (s->core.iter != 0) return fail(ICP_HIP_EINVAL, "set_metric: the session has already stepped");
   if (metric == ICP_METRIC_PLANE) {
     const icp_hip_ctx* c = s->ctx;
     if (c->group) return fail(ICP_HIP_EINVAL, "set_metric: the plane metric does not run on a multi-device context");
     if (c->comm || c->xfn) return fail(ICP_HIP_EINVAL, "set_metric: the plane metric does not run with a communicator");
     if (!c->normals) return fail(ICP_HIP_ENOTREADY, "set_metric: the target has no normals");
+  }
+  if (metric == ICP_METRIC_GICP) {
+    const icp_hip_ctx* c = s->ctx;
+    if (c->group) return fail(ICP_HIP_EINVAL, "set_metric: the generalized-ICP metric does not run on a multi-device context");
+    if (c->comm || c->xfn) return fail(ICP_HIP_EINVAL, "set_metric: the generalized-ICP metric does not run with a communicator");
+    if (!c->normals) return fail(ICP_HIP_ENOTREADY, "set_metric: the target has no normals");
+    if (!c->src_normals) return fail(ICP_HIP_ENOTREADY, "set_metric: the source has no normals");
+    // the session's cumulative transform is the rotation the sums apply to the normals: it must
+    // start where the normals were made
+    if (c->src_normals_moves != c->src_moves)
+      return fail(ICP_HIP_ENOTREADY, "set_metric: the source has moved since its normals were made (estimate or set them again)");
   }
   s->metric = metric;
   return ICP_HIP_OK;
@@ -165,6 +179,13 @@ int icp_session_last_plane(const icp_session* s, icp_plane_sums* out, int32_t* u
   if (!s) return ICP_HIP_EINVAL;
   if (out) *out = s->plane;
   if (used_plane) *used_plane = s->used_plane;
+  return ICP_HIP_OK;
+}
+
+int icp_session_last_gicp(const icp_session* s, icp_gicp_sums* out, int32_t* used) {
+  if (!s) return ICP_HIP_EINVAL;
+  if (out) *out = s->gicp;
+  if (used) *used = s->used_gicp;
   return ICP_HIP_OK;
 }
 
@@ -315,6 +336,29 @@ int icp_session_step(icp_session* s, icp_iteration_record* rec, int32_t* produce
         }
       }
     }
+    if (s->metric == ICP_METRIC_GICP) {
+      // as the plane metric: the point-to-point loop's decisions, the increment from the
+      // generalized-ICP sums about the valid pairs' source centroid. The source's normals are in the
+      // frame the session started in: the rotation since then is the cumulative transform's that
+      // the resident source carries now (before this step's increment).
+      std::memset(&s->gicp, 0, sizeof(s->gicp));
+      s->used_gicp = 0;
+      if (outcome == icp::kStepTransform) {
+        double R[9];
+        for (int r = 0; r < 3; r++)
+          for (int q = 0; q < 3; q++) R[3 * r + q] = Tc_before[4 * r + q];
+        const double eps = s->ctx->gicp_epsilon;
+        const int grc = rejector ? icp_hip_gicp_sums_at(s->ctx, st.centroid_src, R, eps, tau, &s->gicp)
+                                 : icp_hip_gicp_sums(s->ctx, st.centroid_src, R, eps, &s->gicp);
+        if (grc != ICP_HIP_OK) return failed(grc, false);
+        double Tg[16];
+        icp_gicp_solve(&s->gicp, Tg, &s->used_gicp);
+        if (s->used_gicp) {
+          std::memcpy(s->core.T, Tg, sizeof(Tg));
+          icp::svd::mat4_mul(Tg, Tc_before, s->core.Tc);
+        }
+      }
+    }
     emit_iteration(s, iter, outcome, st, s->core.T, s->core.Tc, rec, produced);
   }
   if (done) *done = s->core.done ? 1 : 0;
@@ -335,8 +379,8 @@ static int session_run(icp_session* s, int32_t k, int32_t* steps_done, int32_t* 
   // (icpengine.cpp:160-164; a flag raised from a progress hook stops the next iteration): such a
   // session steps on the host.
   const bool per_iteration_stop = s->h && s->h->stop_flag;
-  // a plane session steps on the host too (its increment is not the device step's), and so does
-  // one with a rejector (its statistics are not the device record's)
+  // a plane or generalized-ICP session steps on the host too (its increment is not the device
+  // step's), and so does one with a rejector (its statistics are not the device record's)
   if (icp_hip_loop_eligible(s->ctx) && !per_iteration_stop && s->metric == ICP_METRIC_POINT &&
       s->reject == ICP_REJECT_SIGMA) {
     std::vector<icp::LoopRec> recs((size_t)icp_hip_ctx::kLoopRing);

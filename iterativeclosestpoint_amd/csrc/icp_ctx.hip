@@ -190,6 +190,7 @@ void icp_hip_destroy(icp_hip_ctx* c) {
   prewalk_destroy(c);
   las_destroy(c);
   reject_destroy(c);
+  gicp_destroy(c);
   free_source(c);
   free_target(c);
   dfree(c->it);

@@ -169,6 +169,18 @@ struct icp_hip_ctx {
   double* plane_parts = nullptr;  // plane_cap parts + the merged sums (kPlaneSums doubles each)
   int64_t plane_cap = 0;
 
+  // --- generalized ICP (ctx_gicp.cpp): the source's normals (slot order, 3 x fp64; null: none; released
+  // with the source), in the frame the source had when they were made; the part sums of
+  // icp_hip_gicp_sums (made at first use, released with the context); the sessions' epsilon.
+  // src_moves counts the transforms applied to the resident source (host bookkeeping only: the
+  // iterate's fused T_apply, icp_hip_apply, a device-loop batch), src_normals_moves its value when
+  // the normals were made.
+  double* src_normals = nullptr;
+  double* gicp_parts = nullptr;  // gicp_cap parts + the merged sums (kGicpSums doubles each)
+  int64_t gicp_cap = 0;
+  double gicp_epsilon = 1e-3;
+  uint64_t src_moves = 0, src_normals_moves = 0;
+
   // --- rejectors (ctx_reject.cpp): the select's histograms and states, and the pair sums' parts
   // (made at first use, released with the context)
   void* select_buf = nullptr;
@@ -297,6 +309,10 @@ int prewalk_launch(icp_hip_ctx* c, const icp::NNLaunch& a);  // after launch_nn 
 
 // --- ctx_plane.cpp
 void plane_free_target(icp_hip_ctx* c);  // free_target's part: the normals and the plane sums' buffers
+
+// --- ctx_gicp.cpp
+void gicp_free_source(icp_hip_ctx* c);  // free_source's part: the source's normals
+void gicp_destroy(icp_hip_ctx* c);      // the sums' buffers released (icp_hip_destroy)
 
 // --- ctx_reject.cpp
 void reject_destroy(icp_hip_ctx* c);  // the rejectors' buffers released (icp_hip_destroy)

@@ -6,13 +6,13 @@
 //   icp_registration [--source Scan_096_origin.las] [--target Scannew_099.las]
 //                    [--sample-rate 50] [--max-iters 20] [--tolerance 1e-2]
 //                    [--outdir .] [--device 0 | --devices 0,1,...] [--device-io] [--pause]
-//                    [--metric point|plane] [--normals-k 16] [--voxel X]
+//                    [--metric point|plane|gicp] [--normals-k 16] [--gicp-epsilon 1e-3] [--voxel X]
 //                    [--sor K,RATIO] [--radius-filter R,MIN] [--trim F | --max-dist D]
 //
 // --trim F registers with the trimmed rejector (icp_engine_run_options, ICP_REJECT_TRIM): each
 // iteration keeps the fraction F, in (0, 1], of its pairs with the smallest residuals, for scans that
 // overlap only partly. --max-dist D keeps the pairs no farther apart than D metres
-// (ICP_REJECT_MAX_DIST). One of the two at most, alone or with --metric plane; one GPU only. The
+// (ICP_REJECT_MAX_DIST). One of the two at most, alone or with --metric plane / gicp; one GPU only. The
 // CLI's rules, decisions and files otherwise. Without the flags every output is unchanged.
 //
 // --voxel X (metres, > 0) reduces each cloud, after the stride sampling, to the centroids of the
@@ -31,6 +31,11 @@
 // --metric plane registers with the point-to-plane step (icp_engine_run_metric, ICP_METRIC_PLANE):
 // the target's normals are estimated from --normals-k neighbours once the target is set; the CLI's
 // rules, decisions and files otherwise. One GPU only. Without the flag every output is unchanged.
+//
+// --metric gicp registers with the generalized-ICP ("plane-to-plane") step (ICP_METRIC_GICP): the
+// normals of the target and of the source are estimated from --normals-k neighbours, after the
+// thinning and the filters and before the loop; --gicp-epsilon E, in [2^-20, 1], is the covariance
+// along a normal (default 1e-3). The CLI's rules, decisions and files otherwise. One GPU only.
 //
 // --devices runs one registration over several GPUs of this process (icp_cli_icp_devices: the
 // source sharded over them, the octree replicated, RCCL all-gathers per iteration).
@@ -68,6 +73,8 @@ struct Args {
   bool pause = false;
   int metric = ICP_METRIC_POINT;
   int normals_k = 16;
+  double gicp_epsilon = 1e-3;
+  bool with_normals() const { return metric == ICP_METRIC_PLANE || metric == ICP_METRIC_GICP; }
   double voxel = 0.0;  // 0: no voxel grid
   int sor_k = 0;       // 0: no statistical filter
   double sor_ratio = 0.0;
@@ -82,7 +89,7 @@ struct Args {
   std::fprintf(code ? stderr : stdout,
                "usage: %s [--source F] [--target F] [--sample-rate N] [--max-iters N] [--tolerance X]\n"
                "          [--outdir D] [--device N | --devices N,M,...] [--device-io] [--pause]\n"
-               "          [--metric point|plane] [--normals-k N] [--voxel X]\n"
+               "          [--metric point|plane|gicp] [--normals-k N] [--gicp-epsilon E] [--voxel X]\n"
                "          [--sor K,RATIO] [--radius-filter R,MIN] [--trim F | --max-dist D]\n",
                prog);
   std::exit(code);
@@ -177,9 +184,19 @@ Args parse(int argc, char** argv) {
       const std::string m = val();
       if (m == "point") a.metric = ICP_METRIC_POINT;
       else if (m == "plane") a.metric = ICP_METRIC_PLANE;
+      else if (m == "gicp") a.metric = ICP_METRIC_GICP;
       else usage(argv[0], 2);
     }
     else if (k == "--normals-k") a.normals_k = (int)std::strtol(val(), nullptr, 10);
+    else if (k == "--gicp-epsilon") {
+      const char* v = val();
+      char* end = nullptr;
+      a.gicp_epsilon = std::strtod(v, &end);
+      if (end == v || *end != '\0' || !(a.gicp_epsilon >= 0x1p-20 && a.gicp_epsilon <= 1.0)) {
+        std::fprintf(stderr, "--gicp-epsilon must be in [2^-20, 1]\n");
+        usage(argv[0], 2);
+      }
+    }
     else if (k == "--pause") a.pause = true;
     else if (k == "-h" || k == "--help") usage(argv[0], 0);
     else usage(argv[0], 2);
@@ -197,11 +214,15 @@ Args parse(int argc, char** argv) {
     std::fprintf(stderr, "--metric plane runs on one GPU (the plane sums are not exchanged between devices)\n");
     usage(argv[0], 2);
   }
+  if (a.metric == ICP_METRIC_GICP && a.devices.size() > 1) {
+    std::fprintf(stderr, "--metric gicp runs on one GPU (the source is sharded, the sums are not exchanged between devices)\n");
+    usage(argv[0], 2);
+  }
   if (a.reject != ICP_REJECT_SIGMA && a.devices.size() > 1) {
     std::fprintf(stderr, "--trim and --max-dist run on one GPU (the residuals are not exchanged between devices)\n");
     usage(argv[0], 2);
   }
-  if (a.metric == ICP_METRIC_PLANE && (a.normals_k < 3 || a.normals_k > ICP_HIP_KNN_MAX)) {
+  if (a.with_normals() && (a.normals_k < 3 || a.normals_k > ICP_HIP_KNN_MAX)) {
     std::fprintf(stderr, "--normals-k must be in [3, %d]\n", ICP_HIP_KNN_MAX);
     std::exit(2);
   }
@@ -361,6 +382,26 @@ icp_run_options cli_options(const Args& a) {
   return o;
 }
 
+void print_metric(const Args& a) {
+  if (a.metric == ICP_METRIC_PLANE)
+    std::cout << "metric: point-to-plane, normals from " << a.normals_k << " neighbours" << std::endl;
+  if (a.metric == ICP_METRIC_GICP)
+    std::cout << "metric: generalized ICP, epsilon " << a.gicp_epsilon << ", normals of both clouds from " << a.normals_k
+              << " neighbours" << std::endl;
+}
+
+// The normals the metric needs: the target's once the target is set, the source's (and the
+// epsilon) once the source is.
+int target_normals(const Args& a, icp_hip_ctx* ctx) {
+  return a.with_normals() ? icp_hip_estimate_target_normals(ctx, a.normals_k, nullptr) : ICP_HIP_OK;
+}
+
+int source_normals(const Args& a, icp_hip_ctx* ctx) {
+  if (a.metric != ICP_METRIC_GICP) return ICP_HIP_OK;
+  const int rc = icp_hip_estimate_source_normals(ctx, a.normals_k, nullptr);
+  return rc == ICP_HIP_OK ? icp_hip_set_gicp_epsilon(ctx, a.gicp_epsilon) : rc;
+}
+
 void print_rejector(const Args& a) {
   if (a.reject == ICP_REJECT_TRIM) std::cout << "rejector: trimmed, keeps " << a.reject_param << " of the pairs" << std::endl;
   if (a.reject == ICP_REJECT_MAX_DIST) std::cout << "rejector: pairs within " << a.reject_param << " m" << std::endl;
@@ -448,10 +489,9 @@ int run_device_io(const Args& a) {
   icp_result res;
   if (icp_hip_set_target_device(ctx, static_cast<double*>(d_tgt), nt, 10, 20, ICP_RULES_CLI) != ICP_HIP_OK)
     return bail("registration failed");
-  if (a.metric == ICP_METRIC_PLANE) {
-    std::cout << "metric: point-to-plane, normals from " << a.normals_k << " neighbours" << std::endl;
-    if (icp_hip_estimate_target_normals(ctx, a.normals_k, nullptr) != ICP_HIP_OK) return bail("cannot estimate the target normals");
-  }
+  print_metric(a);
+  if (target_normals(a, ctx) != ICP_HIP_OK) return bail("cannot estimate the target normals");
+  if (source_normals(a, ctx) != ICP_HIP_OK) return bail("cannot estimate the source normals");
   print_rejector(a);
   const icp_run_options opt = cli_options(a);
   const int rc = a.reject == ICP_REJECT_SIGMA ? icp_engine_run_metric(ctx, &p, a.metric, &res, hist.data(), cap, nullptr)
@@ -479,8 +519,8 @@ int run_device_io(const Args& a) {
   return 0;
 }
 
-// ICP() with the point-to-plane step or a rejector on host clouds: icp_cli_icp_devices' steps on one
-// context, with the normals (plane metric) estimated once the target is set. src is moved in place.
+// ICP() with another metric or a rejector on host clouds: icp_cli_icp_devices' steps on one context,
+// with the metric's normals estimated once the clouds are set. src is moved in place.
 int cli_icp_options(const Args& a, double* src, int64_t ns, const double* tgt, int64_t nt, double R[9], double t[3],
                   double* transforms, int32_t cap, int32_t* n_tr) {
   const icp_params p = cli_params(a);
@@ -489,8 +529,9 @@ int cli_icp_options(const Args& a, double* src, int64_t ns, const double* tgt, i
   icp_hip_ctx* ctx = nullptr;
   int rc = icp_hip_create(&ctx, a.devices[0]);
   if (rc == ICP_HIP_OK) rc = icp_hip_set_target(ctx, tgt, nt, 10, 20, ICP_RULES_CLI);
-  if (rc == ICP_HIP_OK && a.metric == ICP_METRIC_PLANE) rc = icp_hip_estimate_target_normals(ctx, a.normals_k, nullptr);
+  if (rc == ICP_HIP_OK) rc = target_normals(a, ctx);
   if (rc == ICP_HIP_OK) rc = icp_hip_set_source(ctx, src, ns);
+  if (rc == ICP_HIP_OK) rc = source_normals(a, ctx);
   const icp_run_options opt = cli_options(a);
   if (rc == ICP_HIP_OK)
     rc = a.reject == ICP_REJECT_SIGMA ? icp_engine_run_metric(ctx, &p, a.metric, &res, hist.data(), cap, nullptr)
@@ -561,10 +602,9 @@ int main(int argc, char** argv) {
   std::vector<double> transforms((size_t)cap * 16);
   int32_t n_tr = 0;
   if (a.devices.size() > 1) std::cout << "devices: " << a.devices.size() << " GPUs" << std::endl;
-  if (a.metric == ICP_METRIC_PLANE)
-    std::cout << "metric: point-to-plane, normals from " << a.normals_k << " neighbours" << std::endl;
+  print_metric(a);
   print_rejector(a);
-  const int rc = a.metric == ICP_METRIC_PLANE || a.reject != ICP_REJECT_SIGMA
+  const int rc = a.with_normals() || a.reject != ICP_REJECT_SIGMA
                      ? cli_icp_options(a, ss.data(), ns, ts.data(), nt, R, t, transforms.data(), cap, &n_tr)
                      : icp_cli_icp_devices(ss.data(), ns, ts.data(), nt, a.max_iters, a.tolerance, R, t, transforms.data(),
                                            cap, &n_tr, (int)a.devices.size(), a.devices.data());

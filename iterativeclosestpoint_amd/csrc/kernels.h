@@ -256,6 +256,41 @@ hipError_t launch_plane_sums(const PlaneLaunch& a, hipStream_t s);
 // The same sums over the pairs with a finite d <= a.thr.
 hipError_t launch_plane_sums_at(const PlaneLaunch& a, hipStream_t s);
 
+// --- gicp_kernels.hip: the generalized-ICP sums of the last iterate's valid pairs
+// and the source normals between the caller's order and slot order.
+constexpr int kGicpSums = 32;  // 21 of J^T M J (upper triangle, row by row), 6 of J^T M r, r^T M r, n,
+                               // zero source normals, zero target normals, 1 pad
+struct GicpLaunch {
+  const double* x;
+  const double* y;
+  const double* z;
+  const int32_t* pos;
+  const double* dist;
+  const TgtPt* pts;
+  const double* normals;      // the target's, leaf order
+  const double* src_normals;  // the source's, slot order, in the frame they were made in
+  const IterDev* it;          // the threshold
+  double origin[3];
+  double R[9];  // row-major: takes a source normal to the moved source's frame
+  double f;     // 1 - epsilon
+  int64_t n;
+  double* parts;  // gicp_num_parts(n) x kGicpSums
+  double* out;    // kGicpSums
+  double thr;     // launch_gicp_sums_at: the caller's threshold (it is not read)
+};
+int64_t gicp_num_parts(int64_t n);
+hipError_t launch_gicp_sums(const GicpLaunch& a, hipStream_t s);
+// The same sums over the pairs with a finite d <= a.thr.
+hipError_t launch_gicp_sums_at(const GicpLaunch& a, hipStream_t s);
+// slot[k] = aos[perm[k]] (3 x fp64 rows). With bad (null: no check) it also counts in *bad the rows
+// that are neither of unit length nor zero.
+hipError_t launch_src_normals_to_slot(const int32_t* perm, const double* aos, double* slot, int64_t n, unsigned* bad,
+                                      hipStream_t s);
+hipError_t launch_src_normals_from_slot(const int32_t* perm, const double* slot, double* aos, int64_t n,
+                                        hipStream_t s);
+// *bad += the points of an AoS cloud with a non-finite coordinate.
+hipError_t launch_count_nonfinite(const double* aos, int64_t n, unsigned* bad, hipStream_t s);
+
 // --- reject_kernels.hip: the rank select over the residuals and the pair sums at a caller's
 // threshold.
 constexpr int kSelectPasses = 6;   // 11-bit digits of the 64-bit key, the last one 9 bits
