@@ -175,7 +175,12 @@ def tree_model(icp, name):
     points (the device's tight boxes are these rounded outwards to fp32) and its point count; the
     node count and the stack levels (max_inner_depth + 1)."""
     tgt, _, mp, md = FIXTURES[name]
-    t = icp.octree_build(tgt(), mp, md)
+    return tree_model_of(icp, tgt(), mp, md)
+
+
+def tree_model_of(icp, tgt, mp, md):
+    """tree_model of any target (a shifted fixture's: geo_fixtures.py)."""
+    t = icp.octree_build(tgt, mp, md)
     leaf = (t["meta"] & np.uint32(LEAF_BIT)) != 0
     cnt = (t["meta"][leaf] & np.uint32(LEAF_BIT - 1)).astype(np.int64)
     first = t["first"][leaf].astype(np.int64)

@@ -101,9 +101,9 @@ def _far_move():
     return T
 
 
-def _steps(icp, ctx, tgt, src, mp, md, T=None, counters=False):
+def _steps(icp, ctx, tgt, src, mp, md, T=None, counters=False, far_move=None):
     """The four steps in one context. T None: fitted from this context's first iterate (the
-    reference run). Returns the steps' (indices, residuals), the iterates' records, T, the moved
+    reference run). far_move None: _far_move() (a shifted fixture hands in its own). Returns the steps' (indices, residuals), the iterates' records, T, the moved
     sources, the IterStats of the iterates and the counters of each step."""
     ctx.set_target(tgt, mp, md, icp.RULES_ENGINE)
     ctx.set_source(src)
@@ -121,7 +121,7 @@ def _steps(icp, ctx, tgt, src, mp, md, T=None, counters=False):
     if counters:
         both = ctx.debug_counters()  # nn() adds to the last iterate's counters
         dbg.append({k: both[k] - dbg[1][k] for k in both})
-    st2 = ctx.iterate(_far_move(), 2, icp.RULES_ENGINE, 3.0)
+    st2 = ctx.iterate(_far_move() if far_move is None else far_move, 2, icp.RULES_ENGINE, 3.0)
     out.append(ctx.get_correspondences())
     far = ctx.get_source()
     if counters:
@@ -131,9 +131,10 @@ def _steps(icp, ctx, tgt, src, mp, md, T=None, counters=False):
             "levels": ctx.target_info()["stack_levels"], "on_device": ctx.target_build_info()[0]}
 
 
-def _precheck(icp, name, n, tgt, src):
-    """The fixture's CPU pre-checks (they assert). Returns what they measured, for the log."""
-    model = bf.tree_model(icp, name)
+def _precheck(icp, name, n, tgt, src, model=None):
+    """The fixture's CPU pre-checks (they assert). Returns what they measured, for the log. model:
+    the tree model of a shifted target (default: the fixture's own)."""
+    model = bf.tree_model(icp, name) if model is None else model
     info = {"levels": model["levels"], "max_depth": model["max_depth"]}
     if name.startswith("shell"):
         # every query alone overflows its wave (d), so the partial waves need no box check
@@ -153,6 +154,26 @@ def _precheck(icp, name, n, tgt, src):
     return info
 
 
+def _reference_case(icp, oracle, name, n, tgt, src, mp, md, model=None, far_move=None):
+    """A case's clouds, the reference-order context's four steps and, for the small sources, the
+    oracle's answers, after the pre-checks (model, far_move: a shifted fixture's, see _precheck, _steps)."""
+    info = _precheck(icp, name, n, tgt, src, model)
+    print("pre-checks", name, n, info)
+    # the same (host) query order as the contexts under test: the statistics are sums in slot order
+    with icp.Context(0, icp.config(search=icp.SEARCH_REFERENCE, no_warmup=1, query_order=1)) as ctx:
+        ref = _steps(icp, ctx, tgt, src, mp, md, far_move=far_move)
+    assert ref["levels"] == info["levels"] and ref["on_device"] == (md <= bf.GPU_BUILD_MAX_DEPTH), (name, ref["levels"])
+    assert np.all(np.isfinite(ref["T"])) and np.all(np.isfinite(ref["moved"])), name
+    if n <= 1024:
+        tree = oracle.OracleTree(tgt, mp, md)
+        first = tree.nn(src, init_best=oracle.DBL_MAX)
+        ref["oracle"] = [first, tree.nn(ref["moved"], init_best=oracle.DBL_MAX), first,
+                         tree.nn(ref["far"], init_best=oracle.DBL_MAX)]
+    for a in (ref["moved"], ref["far"], *(x for pair in ref["steps"] + ref.get("oracle", []) for x in pair)):
+        a.setflags(write=False)
+    return tgt, src, mp, md, ref
+
+
 @pytest.fixture(scope="module")
 def reference(icp, oracle):
     """(name, n) -> the clouds, the reference-order context's four steps and, for the small
@@ -162,22 +183,7 @@ def reference(icp, oracle):
     def get(name, n):
         if (name, n) in cache:
             return cache[name, n]
-        tgt, src, mp, md = bf.clouds(name, n)
-        info = _precheck(icp, name, n, tgt, src)
-        print("pre-checks", name, n, info)
-        # the same (host) query order as the contexts under test: the statistics are sums in slot order
-        with icp.Context(0, icp.config(search=icp.SEARCH_REFERENCE, no_warmup=1, query_order=1)) as ctx:
-            ref = _steps(icp, ctx, tgt, src, mp, md)
-        assert ref["levels"] == info["levels"] and ref["on_device"] == (md <= bf.GPU_BUILD_MAX_DEPTH), (name, ref["levels"])
-        assert np.all(np.isfinite(ref["T"])) and np.all(np.isfinite(ref["moved"])), name
-        if n <= 1024:
-            tree = oracle.OracleTree(tgt, mp, md)
-            first = tree.nn(src, init_best=oracle.DBL_MAX)
-            ref["oracle"] = [first, tree.nn(ref["moved"], init_best=oracle.DBL_MAX), first,
-                             tree.nn(ref["far"], init_best=oracle.DBL_MAX)]
-        for a in (ref["moved"], ref["far"], *(x for pair in ref["steps"] + ref.get("oracle", []) for x in pair)):
-            a.setflags(write=False)
-        cache[name, n] = (tgt, src, mp, md, ref)
+        cache[name, n] = _reference_case(icp, oracle, name, n, *bf.clouds(name, n))
         return cache[name, n]
 
     return get
@@ -212,7 +218,7 @@ def _direct(n, n_ball, ball_mode):
     return ball_mode == 2 or (ball_mode == 0 and n_ball > 4 * blocks)
 
 
-def _check_counters(errors, icp, name, n, ball_mode, got, tgt, src):
+def _check_counters(errors, icp, name, n, ball_mode, got, tgt, src, model=None):
     """The first iterate's counters against the counts derived in the module docstring."""
     st, c = got["st0"], got["dbg"][0]
     shell = name.startswith("shell")
@@ -234,7 +240,7 @@ def _check_counters(errors, icp, name, n, ball_mode, got, tgt, src):
         want("direct: lane_handed == ball_overflow == ball_points == 0",
              c["lane_handed"] == c["ball_overflow"] == c["ball_points"] == 0)
     if name == "shell_flat" and st.n_ball_search == n_ball:
-        listed = bf.listed_points(bf.tree_model(icp, name), tgt, src)
+        listed = bf.listed_points(bf.tree_model(icp, name) if model is None else model, tgt, src)
         want(f"shell_flat: listed points {listed} <= {bf.BB_PTS} x bb_steps {c['bb_steps']}: no multi-round step proven",
              listed > bf.BB_PTS * c["bb_steps"])
     if name == "shell_ties":
@@ -255,9 +261,13 @@ def _check_counters(errors, icp, name, n, ball_mode, got, tgt, src):
 
 
 def _run(icp, reference, name, n, ball_mode, cell_starts):
-    tgt, src, mp, md, ref = reference(name, n)
+    return _run_case(icp, reference(name, n), name, n, ball_mode, cell_starts)
+
+
+def _run_case(icp, case, name, n, ball_mode, cell_starts, model=None, far_move=None):
+    tgt, src, mp, md, ref = case
     with icp.Context(0, _config(icp, ball_mode, cell_starts)) as ctx:
-        got = _steps(icp, ctx, tgt, src, mp, md, T=ref["T"], counters=True)
+        got = _steps(icp, ctx, tgt, src, mp, md, T=ref["T"], counters=True, far_move=far_move)
     for step, c in zip(STEP_NAMES, got["dbg"]):
         print(f"{name} n {n} ball_mode {ball_mode} cell_starts {cell_starts} {step}:",
               {k: c[k] for k in BALL_COUNTERS})
@@ -267,7 +277,7 @@ def _run(icp, reference, name, n, ball_mode, cell_starts):
           f"ball_queue_off {max(bf.BALL_LDS_FLOOR, 512 * got['levels'])}")
     errors = []
     _compare(errors, got, ref)
-    _check_counters(errors, icp, name, n, ball_mode, got, tgt, src)
+    _check_counters(errors, icp, name, n, ball_mode, got, tgt, src, model)
     return got, errors
 
 

@@ -19,22 +19,28 @@ pytestmark = pytest.mark.gpu
 N = 20_000
 
 
-def _steps(icp, ctx, tgt, src, transforms):
+def _steps(icp, ctx, tgt, src, transforms, after=None):
     """The sequence's (indices, residuals) per step; transforms: the two fitted ones, or None to
-    fit them from this context's own statistics (the reference run)."""
+    fit them from this context's own statistics (the reference run). after(ctx): called once each
+    step has run (test_gpu_geo_search.py reads the moved source and the counters there)."""
     out, fitted = [], []
+    after = after or (lambda ctx: None)
     ctx.set_target(tgt, 10, 20, icp.RULES_ENGINE)
     ctx.set_source(src)
     st = ctx.iterate(None, 0, icp.RULES_ENGINE, 3.0)
     out.append(ctx.get_correspondences())
+    after(ctx)
     for k in (1, 2):
         T = icp.best_fit_from_stats(st) if transforms is None else transforms[k - 1]
         fitted.append(T)
         st = ctx.iterate(T, k, icp.RULES_ENGINE, 3.0)
         out.append(ctx.get_correspondences())
+        after(ctx)
     out.append(ctx.nn(ctx.get_source()))
+    after(ctx)
     ctx.iterate(None, 3, icp.RULES_ENGINE, 3.0)
     out.append(ctx.get_correspondences())
+    after(ctx)
     return out, fitted
 
 
